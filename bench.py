@@ -6,7 +6,7 @@ multi-table forms) with every input array already resident in HBM.  Workload (BA
 8d): 10M resident keys per GPU, ONE Zipf(1.1) request stream over those keys (numpy PCG64 stream seed 1234, permutation
 seed 99), TOKEN_BUCKET, hits 1, limit 100, duration 60 s, now_ms advancing 1 ms per batch.
 
-The stream is NEVER replayed: the timed region is max(--steps, 2048) DISTINCT batches drawn once (134 M requests touching
+The stream is NEVER replayed: the timed region is exactly --steps DISTINCT batches drawn once (at the default 2048: 134 M requests touching
 ~5.6 M distinct keys = ~0.8 GB of table lines at 144 B per key, 1.1 GB in 64-byte sectors — past the 256 MiB Infinity
 Cache), each with its own now_ms.  Warm-up batches, the batches used for per-kernel HIP-event timing and for the
 single-batch latency are further distinct parts of the same stream.  Key ids are drawn on the host (the canonical numpy
@@ -38,7 +38,9 @@ replicated consistent hash (replicated_hash.go; 512 vnodes, fnv1, peers gpu0..gp
 for the keys it owns — no data-path collective (weak scaling).  --global-sync K = BASELINE config 5 on the native exchange
 (guber_comm_* + guber_global_sync: RCCL between ranks, device copies between logical ranks of one GPU).
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0; `ms_per_step` is the wall time of one timed batch.  --dump-outputs DIR writes the answers of the
+last timed batch (what the caller of the timed path receives for it) as DIR/<column>.npy: with the same arguments the inputs are
+the same from run to run, so two builds can be compared answer for answer.
 """
 import argparse
 import ctypes as C
@@ -55,7 +57,6 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 HBM_PEAK_GBPS = 8000.0           # MI355X spec (MI355X_MICROARCH.md)
-MIN_TIMED_BATCHES = 2048         # the timed region is never shorter than this many distinct batches
 BYTES_PER_DECISION = {"token": 149, "leaky": 173}   # SURVEY.md section 8d, 16-byte keys
 # split of the algorithmic bytes over the kernels that touch request / table / response data (DESIGN.md
 # "Algorithmic bytes"): k_front reads key_off 4 + key 16 + table 56 (token) / 64 (leaky); k_eval2 reads
@@ -88,14 +89,14 @@ def host_digest(res):
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2048, help=f"timed batches; at least {MIN_TIMED_BATCHES} distinct batches are always timed")
+    ap.add_argument("--steps", type=int, default=2048, help="timed batches: the timed region is exactly this many distinct batches")
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--keys", type=int, default=10_000_000, help="resident keys per GPU")
     ap.add_argument("--batch", type=int, default=65536)
     ap.add_argument("--algo", choices=["token", "leaky"], default="token")
     ap.add_argument("--dist", choices=["zipf", "uniform"], default="zipf")
     ap.add_argument("--duration-ms", type=int, default=60_000, help="RateLimitReq.duration of the stream")
-    ap.add_argument("--min-batches", type=int, default=MIN_TIMED_BATCHES, help="lower bound of the timed region in distinct batches (measurement scripts may lower it)")
+    ap.add_argument("--min-batches", type=int, default=0, help="accepted and ignored (--steps alone sets the timed region)")
     ap.add_argument("--min-ms", type=float, default=0.0, help="accepted and ignored (the timed region is a fixed number of distinct batches, never a replay)")
     ap.add_argument("--gen-batches", type=int, default=16, help="routed: batches of --batch requests per generation handed to the device-side front (guber_front_*)")
     ap.add_argument("--headline", choices=["routed", "presplit"], default="routed",
@@ -131,7 +132,22 @@ def parse():
                          "GPUs: the key space is ring-peers x --keys, rank r owns what the ring gives gpu<r>")
     ap.add_argument("--one-device", action="store_true",
                     help="debug: all ranks share GPU 0 (single-GPU box; use with --backend gloo)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the answers of the last timed batch (status, err, limit, remaining, reset_time) as DIR/<name>.npy, float64")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.global_sync:
+        ap.error("--dump-outputs covers the headline's timed path, not --global-sync")
+    return args
+
+
+def dump_outputs(d, cols, lo, hi):
+    """the five answer columns of requests lo..hi (what a caller of the timed path receives for its last step) -> d/<name>.npy, float64
+    (every value is an integer below 2**53: exact)"""
+    os.makedirs(d, exist_ok=True)
+    for name in ("status", "err", "limit", "remaining", "reset_time"):
+        np.save(os.path.join(d, f"{name}.npy"), cols[name][lo:hi].cpu().numpy().astype(np.float64))
 
 
 class Ctx:
@@ -613,20 +629,36 @@ class RoutedRig(Rig):
         self.front = self.ga.Front(self.engines, self.place, max_n=self.G, depth=int(os.environ.get("GUBER_BENCH_FRONT_DEPTH", "4")))
 
     def gen_now(self, g, now0):
-        return now0 + 1 + g * self.GB                               # (the clock advances 1 ms per batch of B on average)
+        return now0 + 1 + self.gen_start[g]                         # (the clock advances 1 ms per batch of B on average)
+
+    def _generations(self, total):
+        """start batch of every generation: each segment of measure() (warm-up, timed, profile, latency) is cut into generations of GB
+        batches, the segment's last one shorter when the segment is not a whole number of generations"""
+        segs = [getattr(self, k, 0) for k in ("warmup", "steps", "profile_steps", "latency_steps")]
+        if sum(segs) != total:
+            segs = [total]
+        starts, a = [], 0
+        for n in segs:
+            starts += list(range(a, a + n, self.GB))
+            a += n
+        return starts
 
     def build_stream(self, total, now0, seed):
-        """total = batches of B (a multiple of GB): ONE stream in arrival order, generation g = requests [g*G, (g+1)*G)"""
+        """total = batches of B: ONE stream in arrival order, generation g = batches [gen_start[g], gen_start[g + 1])"""
         torch, B, L, dev, G, GB = self.torch, self.ctx.B, self.L, self.ctx.dev, self.G, self.GB
-        assert total % GB == 0
-        ngen = total // GB
+        self.gen_start = self._generations(total)
+        ngen = len(self.gen_start)
+        bounds = self.gen_start + [total]
+        gen_n = [(bounds[g + 1] - bounds[g]) * B for g in range(ngen)]
+        self.gen_of = {b: g for g, b in enumerate(bounds)}
+        gen_at = [g for g in range(ngen) for _ in range(bounds[g], bounds[g + 1])]
         nk = len(self.ctx.my_ids)
         n = total * B
         if self.dist_kind == "zipf":
             d_ids = ZipfRanker(torch, dev, nk, s=1.1, seed=seed, perm_seed=99).draw_dev(n)
         else:
             d_ids = torch.from_numpy(np.random.default_rng(seed).integers(0, nk, n, dtype=np.int32)).to(dev)
-        self.seq = [(0, self.gen_now(s // GB, now0)) for s in range(total)]
+        self.seq = [(0, self.gen_now(gen_at[s], now0)) for s in range(total)]
         self.h_ids = d_ids.view(total, B).cpu().numpy()
         d_keys = torch.empty(n * L + 16, dtype=torch.uint8, device=dev)
         d_keys[-16:] = 0
@@ -637,7 +669,7 @@ class RoutedRig(Rig):
         self.d_keys = d_keys
         self.distinct_keys = int(torch.unique(d_ids).numel())
         samp = list(range(0, ngen, max(1, ngen // 16)))[:16]            # (a generation touches the tables once per distinct key: its shares have disjoint keys)
-        self.access_frac = float(np.mean([int(torch.unique(d_ids[g * G:(g + 1) * G]).numel()) for g in samp])) / G
+        self.access_frac = float(np.mean([int(torch.unique(d_ids[bounds[g] * B:bounds[g] * B + gen_n[g]]).numel()) / gen_n[g] for g in samp]))
         del d_ids
         t_offG = torch.from_numpy((np.arange(G + 1, dtype=np.int64) * L).astype(np.int32)).to(dev)
         self.cols = {"off": t_offG.repeat(ngen), "hits": torch.full((n,), 1, dtype=torch.int64, device=dev),
@@ -646,16 +678,17 @@ class RoutedRig(Rig):
                      "algorithm": torch.full((n,), self.algo_id, dtype=torch.uint8, device=dev),
                      "behavior": torch.zeros((n,), dtype=torch.int32, device=dev)}
         c, ga = self.cols, self.ga
-        self.gens = [ga.GuberBatch(G, 0, d_keys.data_ptr() + g * G * L, c["off"].data_ptr() + g * (G + 1) * 4, c["hits"].data_ptr() + g * G * 8,
-                                   c["limit"].data_ptr() + g * G * 8, c["duration"].data_ptr() + g * G * 8, None, None, c["algorithm"].data_ptr() + g * G,
-                                   c["behavior"].data_ptr() + g * G * 4, None, None, None, int(self.gen_now(g, now0))) for g in range(ngen)]
+        o = [b * B for b in bounds]                                     # a generation's first request
+        self.gens = [ga.GuberBatch(gen_n[g], 0, d_keys.data_ptr() + o[g] * L, c["off"].data_ptr() + g * (G + 1) * 4, c["hits"].data_ptr() + o[g] * 8,
+                                   c["limit"].data_ptr() + o[g] * 8, c["duration"].data_ptr() + o[g] * 8, None, None, c["algorithm"].data_ptr() + o[g],
+                                   c["behavior"].data_ptr() + o[g] * 4, None, None, None, int(self.gen_now(g, now0))) for g in range(ngen)]
         # every generation writes its own answer arrays (request order); every timed slice of B is digest-checked afterwards
         self.res_all = {"status": torch.empty(n, dtype=torch.uint8, device=dev), "err": torch.empty(n, dtype=torch.uint8, device=dev),
                         "limit": torch.empty(n, dtype=torch.int64, device=dev), "remaining": torch.empty(n, dtype=torch.int64, device=dev),
                         "reset_time": torch.empty(n, dtype=torch.int64, device=dev)}
         r = self.res_all
-        self.gres = [ga.GuberResult(r["status"].data_ptr() + g * G, r["limit"].data_ptr() + g * G * 8, r["remaining"].data_ptr() + g * G * 8,
-                                    r["reset_time"].data_ptr() + g * G * 8, r["err"].data_ptr() + g * G, 0, 0, 0, 0, 0) for g in range(ngen)]
+        self.gres = [ga.GuberResult(r["status"].data_ptr() + o[g], r["limit"].data_ptr() + o[g] * 8, r["remaining"].data_ptr() + o[g] * 8,
+                                    r["reset_time"].data_ptr() + o[g] * 8, r["err"].data_ptr() + o[g], 0, 0, 0, 0, 0) for g in range(ngen)]
         torch.cuda.synchronize(dev)
 
     def keep_results(self, which):
@@ -668,9 +701,8 @@ class RoutedRig(Rig):
         self.kept = {s: self.SliceResult(self, k) for k, s in enumerate(which)}
 
     def run(self, lo, hi, timed=False):
-        torch, GB = self.torch, self.GB
-        assert lo % GB == 0 and hi % GB == 0
-        g0, g1 = lo // GB, hi // GB
+        torch = self.torch
+        g0, g1 = self.gen_of[lo], self.gen_of[hi]                      # (KeyError: lo / hi is not a generation boundary)
         N = g1 - g0
         ba = (self.ga.GuberBatch * max(N, 1))(*self.gens[g0:g1])
         ra = (self.ga.GuberResult * max(N, 1))(*self.gres[g0:g1])
@@ -709,9 +741,8 @@ class RoutedRig(Rig):
 
     def latency(self):
         """one generation at a time, nothing else in flight: the call -> the answers in HBM (host clock: enqueue included)"""
-        GB = self.GB
-        lo = (self.warmup + self.steps + self.profile_steps) // GB
-        hi = lo + self.latency_steps // GB
+        a = self.warmup + self.steps + self.profile_steps
+        lo, hi = self.gen_of[a], self.gen_of[a + self.latency_steps]
         lat = []
         for g in range(lo, hi):
             ba, ra = (self.ga.GuberBatch * 1)(self.gens[g]), (self.ga.GuberResult * 1)(self.gres[g])
@@ -960,7 +991,7 @@ def main():
     routed = args.headline == "routed"
     GB = max(1, args.gen_batches) if routed else 1
     up = lambda v: -(-int(v) // GB) * GB                              # noqa: E731  (whole generations)
-    steps = up(max(args.steps, args.min_batches))
+    steps = args.steps                                                # (the last generation of the timed region may be short)
     rig = RoutedRig(ctx, args.algo, args.dist, S, GB, duration_ms=args.duration_ms) if routed else Rig(ctx, args.algo, args.dist, S, duration_ms=args.duration_ms)
     resident = rig.populate(NOW0)
     if os.environ.get("GUBER_BENCH_EXIT_AFTER_SETUP"):              # scripts/gpu_r06_fault.sh: many fresh starts of the set-up phase
@@ -975,6 +1006,8 @@ def main():
     # the timed region (measured: 9.4-9.6 instead of 10.0-10.2 G/s, profiles/r05_t_*).  At least four batches per shard run untimed.
     warm = up(max(args.warmup, 4 * S))
     m = rig.measure(steps, warm, NOW0, seed, profile_steps=up(max(0, args.profile_steps)), latency_steps=up(max(0, args.latency_steps)))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rig.res_cols, (steps - 1) * B, steps * B)    # (res_cols: the timed batches' answers, in order)
 
     if os.environ.get("GUBER_BENCH_EXIT_AFTER_TIMED"):              # scripts/gpu_r06_fault.sh: many fresh starts up to the end of the timed region
         print(json.dumps({"timed_only": True, "value": m["value"]}), flush=True)
@@ -1171,8 +1204,7 @@ def main():
             "timed_region": {"distinct_batches": steps, "replays": 0, "ms": round(m["timed_ms"], 3), "untimed_batches_before": warm,
                              "untimed_note": (f"--warmup {args.warmup} was raised to {warm} untimed batches (four per shard: every shard, stream and kernel has run before the clock starts)"
                                               if warm != args.warmup else "the untimed batches are the --warmup asked for"),
-                             "note": (f"--steps {args.steps} was raised to {steps}: the timed region is never shorter than {args.min_batches} distinct batches"
-                                      if steps != args.steps else "every timed batch is a distinct part of the stream"),
+                             "note": "every timed batch is a distinct part of the stream",
                              "ms_per_step_hip_events": round(m["ms_per_step_events"], 5), "host_enqueue_ms": round(m["enqueue_ms"], 3), "host_enqueue_busy_ms": round(m["enqueue_busy_ms"], 3),
                              "host_enqueue_note": "wall time of the ONE dispatcher call that enqueues the whole timed region, and the CPU time its thread burnt in it (busy << wall: it waits for queue room, the GPU is the bound; busy ~ wall: the host is)",
                              "front": front_stats,

@@ -25,13 +25,20 @@ callers of GPUWorkerPool do it while they write their requests into the shard's 
 
 Timing: all timed batches are enqueued by ONE dispatcher call (guber_eval_batches_routed_dev: round by round the next batch
 of every shard; shards that share a stream — 12 shards over 3 streams by default — share their two launches), bracketed by
-barrier + device synchronize; nothing is created or allocated inside.  Parity is checked over the TIMED work: the oracle
-is fed the whole stream (populate, warm-up, every timed batch, in order) and every 64th timed batch's answers (plus the
-first 8 and the last) must equal the oracle's element-wise; the engine's internal-retry counter must not have moved.
+barrier + device synchronize; nothing is created or allocated inside.
 
-Extras in the same JSON line: `leaky` (configs[2], parity-gated), `expiring` (duration 500 ms: every bucket expires and is
-renewed several times under the clock), `shards_1`, `uniform` (no skew), `end_to_end` (host memory in / out, PCIe
-included), `pool` (caller threads -> V1Instance::GetRateLimits -> the C++ GPUWorkerPool, 10 M keys).
+A plain run does only what the headline figure needs: set-up, warm-up, the timed region, --dump-outputs, the JSON line.  --full
+adds everything else, as separate work after the timed region (or, for the box's ceilings, before the stream is built):
+  * parity over the TIMED work: the oracle is fed the whole stream (populate, warm-up, every timed batch, in order) and every
+    timed batch's answers must equal the oracle's (digest, element-wise on a mismatch); the engine's internal-retry counter must
+    not have moved.  No number is printed if this fails;
+  * the CPU baseline (the oracle's thread sweep), the roofline (per-kernel HIP-event timing of a profile segment, the box's
+    measured ceilings from tools/random_access, the committed PMC figures) and the single-batch latency;
+  * extras in the same JSON line: `leaky` (configs[2], parity-gated), `expiring` (duration 500 ms: every bucket expires and is
+    renewed several times under the clock), `shards_1`, `uniform` (no skew), `end_to_end` (host memory in / out, PCIe
+    included), `pool` (caller threads -> V1Instance::GetRateLimits -> the C++ GPUWorkerPool, 10 M keys), and the N > 1 rehearsals.
+The profile and latency segments are drawn after the timed batches, so the warm-up and timed batches, their clocks and their
+answers are the same with and without --full.
 
 N > 1 (launched by torch.distributed.run, one rank per GPU): the key space is N x 10M keys sharded by the reference's
 replicated consistent hash (replicated_hash.go; 512 vnodes, fnv1, peers gpu0..gpuN-1), every rank evaluates the requests
@@ -102,8 +109,11 @@ def parse():
     ap.add_argument("--headline", choices=["routed", "presplit"], default="routed",
                     help="routed (the all-inclusive arrangement): ONE raw request stream in arrival order -> routed to the shards on the device -> answers in request "
                          "order, inside the clock; presplit: rounds 2-5's headline (per-shard batches split outside the clock, answers left in shard order)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: parity against the oracle, CPU baseline, roofline, latency, the box's ceilings and the "
+                         "--extras (a plain run sets up, warms up, times --steps batches, writes --dump-outputs and prints the line)")
     ap.add_argument("--extras", default="presplit,routed_leaky,leaky,expiring,shards_1,uniform,end_to_end,pool,global_sync,two_ranks",
-                    help="comma list of extra configurations measured after the headline one (N = 1 only); '' = none")
+                    help="with --full: comma list of extra configurations measured after the headline one (N = 1 only); '' = none")
     ap.add_argument("--extra-batches", type=int, default=1024, help="timed distinct batches of the extra configurations")
     ap.add_argument("--dispatch", choices=["threads", "one"], default="one",
                     help="who enqueues the shards' batches: one pre-started thread per shard, or ONE dispatcher for all shards in flush order "
@@ -112,13 +122,13 @@ def parse():
                     help="placement of a GPU's keys on its logical shards: guber_placement fitted to a sample of earlier traffic, or its "
                          "untouched initial table (XXH64 ranges = the reference's getWorker)")
     ap.add_argument("--streams", type=int, default=3, help="with --dispatch one: streams the shards are spread over (shards of one stream share launches)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline AND the oracle parity pass")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline AND the oracle parity pass")
     ap.add_argument("--cpu-seconds", type=float, default=3.0, help="CPU time budget per thread count of the baseline")
     ap.add_argument("--cpu-threads", default="1,8,16,64,all", help="worker shards / threads of the CPU baseline (comma list, 'all' = every host core)")
     ap.add_argument("--profile-steps", type=int, default=4096,
-                    help="further distinct batches run once more, dispatched like the timed region, with HIP events around every launch: the per-kernel "
+                    help="with --full: further distinct batches run once more, dispatched like the timed region, with HIP events around every launch: the per-kernel "
                          "durations and the batch latency under load (4096 batches = >= 1000 pipeline passes of up to four tables)")
-    ap.add_argument("--latency-steps", type=int, default=1024, help="distinct batches run one at a time for the single-batch latency")
+    ap.add_argument("--latency-steps", type=int, default=1024, help="with --full: distinct batches run one at a time for the single-batch latency")
     ap.add_argument("--shards", type=int, default=12, metavar="S",
                     help="logical key-space shards per GPU (the reference's Config.Workers sharding, workers.go:19-25): S "
                          "engines with their own tables, the stream routed to them key by key")
@@ -987,7 +997,8 @@ def main():
 
     S = max(1, args.shards)
     seed = 1234 + rank * 64
-    ctx.ceil = measure_ceilings(K) if (rank == 0 and world == 1) else None
+    full = args.full
+    ctx.ceil = measure_ceilings(K) if (full and rank == 0 and world == 1) else None
     routed = args.headline == "routed"
     GB = max(1, args.gen_batches) if routed else 1
     up = lambda v: -(-int(v) // GB) * GB                              # noqa: E731  (whole generations)
@@ -1005,7 +1016,9 @@ def main():
     # (nor every stream with every kernel) before the clock starts — the first process on a fresh box then pays first-use costs inside
     # the timed region (measured: 9.4-9.6 instead of 10.0-10.2 G/s, profiles/r05_t_*).  At least four batches per shard run untimed.
     warm = up(max(args.warmup, 4 * S))
-    m = rig.measure(steps, warm, NOW0, seed, profile_steps=up(max(0, args.profile_steps)), latency_steps=up(max(0, args.latency_steps)))
+    # (the profile and latency segments follow the timed batches in the stream: without them the batches before are the same)
+    m = rig.measure(steps, warm, NOW0, seed, profile_steps=up(max(0, args.profile_steps)) if full else 0,
+                    latency_steps=up(max(0, args.latency_steps)) if full else 0)
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, rig.res_cols, (steps - 1) * B, steps * B)    # (res_cols: the timed batches' answers, in order)
 
@@ -1014,7 +1027,7 @@ def main():
         os._exit(0)
     roofline = latency = cpu = parity = None
     extras = {}
-    if rank == 0:
+    if rank == 0 and full:
         # ---- per-kernel durations: HIP events around every launch of the profile segment, dispatched like the timed region ----
         fused = args.dispatch == "one" and S > 1
         kernel_ms, per_launch, launches = rig.kernel_profile()
@@ -1090,7 +1103,7 @@ def main():
     # ---- parity over the timed work on EVERY rank (ranks own disjoint keys, replicated_hash.go:104-119: each checks its own timed
     # stream against its own oracle) + the CPU baseline (rank 0; the W sweep at N = 1 only) ---------------------------
     parity_by_rank = None
-    if world > 1 and not args.no_cpu_baseline:
+    if full and world > 1 and not args.no_cpu_baseline:
         import support
         gate_w = min(os.cpu_count() or 1, 32)
         th = max(1, min(gate_w, usable_cpus() // world))                     # (the ranks run their passes at the same time on one host)
@@ -1112,7 +1125,7 @@ def main():
                    "host": {"cpus": os.cpu_count(), "usable": ucpu},
                    "sample": f"rank 0's parity pass: all {steps} timed batches of {B} ({el:.1f} s), {K} resident keys, W = {gate_w} worker caches on {th} threads "
                              f"while the other {world - 1} rank(s) ran theirs on the same host (the N = 1 line carries the thread sweep)"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import support
         ncpu = os.cpu_count() or 1
         ucpu = usable_cpus()
@@ -1184,7 +1197,7 @@ def main():
     torch.cuda.empty_cache()
 
     # ---- extras (rank 0 of a 1-GPU run): other configurations, same machinery ----
-    if rank == 0 and world == 1 and args.extras:
+    if full and rank == 0 and world == 1 and args.extras:
         want = [x.strip() for x in args.extras.split(",") if x.strip()]
         for name in want:
             try:
@@ -1214,8 +1227,9 @@ def main():
                                          else f"one dispatcher for {S} shards over {args.streams} stream(s) (guber_eval_batches_routed_dev: batches of shards that share a stream share launches)"),
                              "shard_streams": m["shard_streams"]},
             "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "parity_batches_by_rank": parity_by_rank, "batch_latency": latency,
+            "full": full,
         }
-        if world > 1 and parity is None and not args.no_cpu_baseline:
+        if full and world > 1 and parity is None and not args.no_cpu_baseline:
             raise SystemExit("no parity verdict for an N > 1 run: refusing to report a number")
         out.update(extras)
         if routed and isinstance(extras.get("presplit"), dict) and extras["presplit"].get("value"):
@@ -1339,7 +1353,7 @@ def run_rehearsal(name, args):
         cmd = ["--gpus", "1", "--global-sync", "8", "--logical-ranks", "2", "--keys", str(args.keys), "--steps", "64", "--warmup", "8"]
     else:
         cmd = ["--gpus", "2", "--one-device", "--backend", "gloo", "--ring-peers", "8", "--keys", str(args.keys), "--steps", "256", "--min-batches", "256", "--warmup", "8",
-               "--extras", "", "--profile-steps", "0", "--latency-steps", "0", "--cpu-threads", "16", "--cpu-seconds", "1"]
+               "--full", "--extras", "", "--profile-steps", "0", "--latency-steps", "0", "--cpu-threads", "16", "--cpu-seconds", "1"]
     p = subprocess.run([sys.executable, os.path.abspath(__file__)] + cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     if p.returncode != 0 or len(lines) != 1:

@@ -12,7 +12,7 @@ NB=${2:-256}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-HEAD="--no-cpu-baseline --extras="
+HEAD="--full --no-cpu-baseline --extras="
 for cfg in "routed:" "presplit:--headline presplit" "shards_1:--headline presplit --shards 1 --min-batches 1024 --steps 1024"; do
   name=${cfg%%:*}; extra=${cfg#*:}
   rm -rf $O/trace_$name

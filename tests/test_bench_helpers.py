@@ -1,7 +1,8 @@
-"""bench.py's host-side arithmetic (no GPU): what `roofline.traffic` is made of."""
+"""bench.py's host-side pieces (no GPU): what `roofline.traffic` is made of, and what a plain run leaves out without changing the timed work."""
 import importlib.util
 import json
 import os
+import sys
 
 from support import ROOT
 
@@ -35,3 +36,43 @@ def test_roofline_traffic_is_the_mix_of_pipelines_the_profile_segment_ran():
     assert set(real["token"]) >= {"k_front", "k_eval2", "k_part", "k_own", "k_eval3"} and set(real["token_fused"]) >= {"k_part", "k_own", "k_eval3"}
     got = b.pipeline_traffic(real, "token", list(launches), launches, per_launch, B)
     assert 149 * B < got < 4 * 149 * B
+
+
+def test_segments_after_the_timed_region_leave_the_timed_batches_alone():
+    """a plain run draws no profile or latency segment, --full draws both after the timed batches: the warm-up and timed batches,
+    their generations and their clocks must come out the same either way (the same answers, the same --dump-outputs)"""
+    import numpy as np
+    import torch
+    b = _bench()
+    # the routed headline: one stream, drawn in chunks from the canonical generator and ranked on the device (here: the CPU)
+    full = b.ZipfRanker(torch, "cpu", 5000, seed=1234).draw_dev(7000, chunk=1024)
+    plain = b.ZipfRanker(torch, "cpu", 5000, seed=1234).draw_dev(3000, chunk=1024)
+    assert torch.equal(full[:3000], plain)
+    # ... cut into generations segment by segment
+    rig = b.RoutedRig.__new__(b.RoutedRig)
+    rig.GB = 16
+    for warm, steps in ((48, 2048), (48, 100), (16, 1)):
+        rig.warmup, rig.steps, rig.profile_steps, rig.latency_steps = warm, steps, 4096, 1024
+        with_segments = rig._generations(warm + steps + 4096 + 1024)
+        rig.profile_steps = rig.latency_steps = 0
+        without = rig._generations(warm + steps)
+        assert with_segments[:len(without)] == without and with_segments[len(without)] == warm + steps
+    # the pre-split arrangement: the first `total` batches in flush order do not depend on how far past them the stream was drawn
+    S, B = 4, 64
+    ids = torch.from_numpy(np.random.default_rng(5).integers(0, 1000, (60 + 2 * S + 2) * B).astype(np.int64))
+    sown = torch.from_numpy((np.arange(1000) % S).astype(np.uint8))
+    long_ids, long_sh = b.split_stream(torch, ids, sown, S, B, 60)
+    short_ids, short_sh = b.split_stream(torch, ids[:(20 + 2 * S + 2) * B], sown, S, B, 20)
+    assert torch.equal(long_ids[:20], short_ids) and long_sh[:20] == short_sh
+
+
+def test_the_plain_run_is_the_default():
+    b = _bench()
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"]
+        assert b.parse().full is False
+        sys.argv.append("--full")
+        assert b.parse().full is True
+    finally:
+        sys.argv = argv

@@ -2,7 +2,7 @@
 
   * `python bench.py --gpus 2 ...` invoked PLAINLY (no WORLD_SIZE: the shape of the driver's 1-GPU command) re-executes itself under
     torch.distributed.run, one rank per "GPU" (--one-device: both ranks on GPU 0, --backend gloo for the timing collectives);
-  * every rank digest-checks its own timed stream against its own oracle — the ranks own disjoint keys on the reference's ring
+  * with --full, every rank digest-checks its own timed stream against its own oracle — the ranks own disjoint keys on the reference's ring
     (replicated_hash.go:104-119) — and rank 0 prints `parity: "2/2 ranks, K/K timed batches each"`, a cpu_baseline and the roofline
     object; a line without a parity verdict is refused;
   * the aggregate of two ranks that SHARE one GPU is compared with the N = 1 run of the same flags (they time-slice one device: the
@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 FAKE = os.path.join(HERE, "hostsim", "libfake_rccl.so")
-COMMON = ["--keys", "2000000", "--min-batches", "256", "--steps", "256", "--warmup", "8", "--extras", "", "--latency-steps", "0", "--profile-steps", "32",
+COMMON = ["--full", "--keys", "2000000", "--min-batches", "256", "--steps", "256", "--warmup", "8", "--extras", "", "--latency-steps", "0", "--profile-steps", "32",
           "--cpu-threads", "8", "--cpu-seconds", "1"]
 
 

@@ -1,10 +1,13 @@
 // wire_server.go — the payload stage behind the gRPC server: the handler registered in V1_ServiceDesc's place never unmarshals, it hands the
 // bytes of the GetRateLimitsReq to guber_wire_pool_get_rate_limits and returns the bytes of the GetRateLimitsResp (include/guber_wire.h,
 // INTEGRATION.md section 3g).  What it replaces: _V1_GetRateLimits_Handler (gubernator_grpc.pb.go:111-127) + V1Instance.GetRateLimits
-// (gubernator.go:183-306) for requests this instance owns; _PeersV1_GetPeerRateLimits_Handler (peers_grpc.pb.go:109) likewise.
+// (gubernator.go:183-306) for requests this instance owns; _PeersV1_GetPeerRateLimits_Handler (peers_grpc.pb.go:109) +
+// V1Instance.GetPeerRateLimits (gubernator.go:462-539) through guber_wire_pool_get_peer_rate_limits; _PeersV1_UpdatePeerGlobals_Handler +
+// V1Instance.UpdatePeerGlobals (gubernator.go:425-459) through guber_wire_pool_update_peer_globals.
 //
 // NOT compiled in this repository (no Go toolchain in the build image): the calls below are made, in the same order and with the same
-// arguments, by tests/hostsim/abi_c99.c (wire_pool_sequence) — compiled as C99 against the public headers and run on the GPU.
+// arguments, by tests/hostsim/abi_c99.c (wire_pool_sequence) and tests/hostsim/peer_abi_c99.c (the two peer handlers) — compiled as C99
+// against the public headers and run on the GPU.
 package gubernator
 
 /*
@@ -22,15 +25,29 @@ import (
 	"google.golang.org/grpc"
 	"google.golang.org/grpc/codes"
 	"google.golang.org/grpc/status"
+	"google.golang.org/protobuf/proto"
 )
 
 // rawMessage is a message that IS its bytes; rawCodec leaves it alone (grpc.ForceServerCodec(rawCodec{}) on the servers of daemon.go:119-144).
+// Everything else — HealthCheck keeps its generated handler, and so does any method a daemon does not hand to the payload stage — is a
+// generated message and goes through the protobuf runtime as under the default codec.
 type rawMessage struct{ b []byte }
 type rawCodec struct{}
 
-func (rawCodec) Marshal(v interface{}) ([]byte, error)   { return v.(*rawMessage).b, nil }
-func (rawCodec) Unmarshal(d []byte, v interface{}) error { v.(*rawMessage).b = d; return nil }
-func (rawCodec) Name() string                             { return "proto" }
+func (rawCodec) Marshal(v interface{}) ([]byte, error) {
+	if m, ok := v.(*rawMessage); ok {
+		return m.b, nil
+	}
+	return proto.Marshal(v.(proto.Message))
+}
+func (rawCodec) Unmarshal(d []byte, v interface{}) error {
+	if m, ok := v.(*rawMessage); ok {
+		m.b = d
+		return nil
+	}
+	return proto.Unmarshal(d, v.(proto.Message))
+}
+func (rawCodec) Name() string { return "proto" }
 
 // WireServer owns the payload stage of ONE device.
 type WireServer struct {
@@ -50,8 +67,10 @@ func NewWireServer(engines []*C.guber_engine_t, rule *C.struct_guber_route_rule)
 // Close: no call may be in flight or arrive any more (the gRPC servers have been stopped: daemon.go Close).
 func (s *WireServer) Close() { C.guber_wire_pool_destroy(s.pool) }
 
-// call hands one serialized message over and returns the serialized answer; wrap: gubernator.go:250-255 (client RPC) or bare texts (peer RPC).
-func (s *WireServer) call(in []byte, wrap C.int) ([]byte, error) {
+// call hands one serialized message over and returns the serialized answer.  peer: the message is a GetPeerRateLimitsReq and is answered as
+// V1Instance.GetPeerRateLimits answers it (no validation, DRAIN_OVER_LIMIT on forwarded GLOBAL items, its error texts); otherwise the client
+// RPC with the error texts of gubernator.go:250-255.
+func (s *WireServer) call(in []byte, peer bool) ([]byte, error) {
 	if len(in) == 0 {
 		return nil, nil // no requests: an empty GetRateLimitsResp
 	}
@@ -59,26 +78,35 @@ func (s *WireServer) call(in []byte, wrap C.int) ([]byte, error) {
 	out := make([]byte, int(C.guber_wire_pool_response_bound(p, C.size_t(len(in)))))
 	var n C.size_t
 	// blocks (a cgo call: the goroutine keeps its thread) until the stage the payload joined has been through the GPU
-	rc := C.guber_wire_pool_get_rate_limits(s.pool, p, C.size_t(len(in)), 1, wrap, (*C.uint8_t)(unsafe.Pointer(&out[0])), C.size_t(len(out)), &n)
+	var rc C.int
+	if peer {
+		rc = C.guber_wire_pool_get_peer_rate_limits(s.pool, p, C.size_t(len(in)), (*C.uint8_t)(unsafe.Pointer(&out[0])), C.size_t(len(out)), &n)
+	} else {
+		rc = C.guber_wire_pool_get_rate_limits(s.pool, p, C.size_t(len(in)), 1, 1, (*C.uint8_t)(unsafe.Pointer(&out[0])), C.size_t(len(out)), &n)
+	}
 	switch rc {
 	case C.GUBER_OK:
 		return out[:int(n)], nil
-	case C.GUBER_E_WIRE_TOO_LARGE: // gubernator.go:189-193
+	case C.GUBER_E_WIRE_TOO_LARGE:
+		if peer { // gubernator.go:464-467
+			return nil, status.Errorf(codes.OutOfRange, "'PeerRequest.rate_limits' list too large; max size is '%d'", maxBatchSize)
+		}
+		// gubernator.go:189-193
 		return nil, status.Errorf(codes.OutOfRange, "Requests.RateLimits list too large; max size is '%d'", maxBatchSize)
 	case C.GUBER_E_WIRE_MALFORMED: // what protobuf-go's Unmarshal failure becomes in grpc-go
 		return nil, status.Error(codes.Internal, "grpc: error unmarshalling request")
 	default:
-		return nil, status.Errorf(codes.Internal, "guber_wire_pool_get_rate_limits: %s", C.GoString(C.guber_last_error()))
+		return nil, status.Errorf(codes.Internal, "guber_wire_pool: %s", C.GoString(C.guber_last_error()))
 	}
 }
 
-// The two method handlers, with the signature grpc.MethodDesc.Handler wants (gubernator_grpc.pb.go:150-165, peers_grpc.pb.go:148-163).
+// The method handlers, with the signature grpc.MethodDesc.Handler wants (gubernator_grpc.pb.go:150-165, peers_grpc.pb.go:148-163).
 func (s *WireServer) getRateLimits(_ interface{}, _ context.Context, dec func(interface{}) error, _ grpc.UnaryServerInterceptor) (interface{}, error) {
 	in := new(rawMessage)
 	if err := dec(in); err != nil {
 		return nil, err
 	}
-	out, err := s.call(in.b, 1)
+	out, err := s.call(in.b, false)
 	return &rawMessage{out}, err
 }
 
@@ -87,11 +115,33 @@ func (s *WireServer) getPeerRateLimits(_ interface{}, _ context.Context, dec fun
 	if err := dec(in); err != nil {
 		return nil, err
 	}
-	out, err := s.call(in.b, 0)
+	out, err := s.call(in.b, true)
 	return &rawMessage{out}, err
 }
 
-// ServiceDescs: V1_ServiceDesc / PeersV1_ServiceDesc with the two hot methods replaced (HealthCheck, UpdatePeerGlobals keep the generated handlers).
+// updatePeerGlobals: the owner's broadcast of GLOBAL buckets (raw bytes in), installed where the pool keeps GLOBAL state; the answer is the
+// empty UpdatePeerGlobalsResp (gubernator.go:458).
+func (s *WireServer) updatePeerGlobals(_ interface{}, _ context.Context, dec func(interface{}) error, _ grpc.UnaryServerInterceptor) (interface{}, error) {
+	in := new(rawMessage)
+	if err := dec(in); err != nil {
+		return nil, err
+	}
+	if len(in.b) == 0 {
+		return &rawMessage{}, nil // no globals
+	}
+	var installed C.uint32_t
+	switch rc := C.guber_wire_pool_update_peer_globals(s.pool, (*C.uint8_t)(unsafe.Pointer(&in.b[0])), C.size_t(len(in.b)), &installed); rc {
+	case C.GUBER_OK:
+		return &rawMessage{}, nil
+	case C.GUBER_E_WIRE_MALFORMED:
+		return nil, status.Error(codes.Internal, "grpc: error unmarshalling request")
+	default: // gubernator.go:452-455
+		return nil, status.Errorf(codes.Internal, "Error in workerPool.AddCacheItem: %s", C.GoString(C.guber_last_error()))
+	}
+}
+
+// ServiceDescs: V1_ServiceDesc / PeersV1_ServiceDesc with GetRateLimits, GetPeerRateLimits and UpdatePeerGlobals replaced (HealthCheck keeps its
+// generated handler: rawCodec hands generated messages to the protobuf runtime).
 func (s *WireServer) ServiceDescs() (grpc.ServiceDesc, grpc.ServiceDesc) {
 	v1, peers := V1_ServiceDesc, PeersV1_ServiceDesc
 	v1.Methods = append([]grpc.MethodDesc(nil), v1.Methods...)
@@ -104,6 +154,9 @@ func (s *WireServer) ServiceDescs() (grpc.ServiceDesc, grpc.ServiceDesc) {
 	for i := range peers.Methods {
 		if peers.Methods[i].MethodName == "GetPeerRateLimits" {
 			peers.Methods[i].Handler = s.getPeerRateLimits
+		}
+		if peers.Methods[i].MethodName == "UpdatePeerGlobals" {
+			peers.Methods[i].Handler = s.updatePeerGlobals
 		}
 	}
 	return v1, peers

@@ -25,6 +25,7 @@ namespace guber {
 
 constexpr int32_t WIRE_OK = 0, WIRE_MALFORMED = -20, WIRE_TOO_LARGE = -21;      // = GUBER_E_WIRE_* (include/guber_wire.h)
 constexpr uint8_t WIRE_PRE_DEAD = 255;                                           // an item of an RPC that turned out malformed
+constexpr uint8_t WIRE_RPC_OWNER = 1, WIRE_RPC_PEER = 2;                         // = GUBER_WIRE_RPC_* (include/guber_wire.h): the bits of WireIn::rpc_owner
 
 // The top level of one payload: field 1 (LEN) = one RateLimitReq; anything else is an unknown field, skipped by wire type.
 // Rd::peek8(pos) = the 8 bytes at pos (zero beyond the payload); Rd::slow(pos) = a plain pointer into the payload for the rare
@@ -87,7 +88,7 @@ struct WireIn {
     const uint8_t* buf;             // the payloads back to back (16 readable bytes past the end)
     const uint32_t* rpc_off;        // [nrpc] where each payload starts in buf (16-byte aligned)
     const uint32_t* rpc_len;        // [nrpc]
-    const uint8_t* rpc_owner;       // [nrpc] RateLimitReqState.IsOwner of the RPC's items
+    const uint8_t* rpc_owner;       // [nrpc] flag byte: bit 0 RateLimitReqState.IsOwner of the RPC's items, bit 1 the peer RPC (implies owner)
     uint32_t nrpc, cap_per_rpc;     // records per RPC the scratch holds
     uint32_t max_per_rpc;           // 0 = no cap (gubernator.go:40 passes 1000)
     uint32_t cap_items;             // items the output arrays hold
@@ -511,9 +512,9 @@ __global__ __launch_bounds__(256) void k_wire_fill(WireIn in, WireScratch sc, Wi
     }
     uint8_t pre = 0;
     uint32_t klen = 0;
+    // (the key row is written for empty halves too — "name_", "_ukey", "_": the peer RPC evaluates those; the client RPC's verdict on them falls
+    //  below, where the RPC's flag byte is loaded, as late as it always was: nothing of it is live across parse_req)
     if (!ok) pre = WIRE_PRE_DEAD;
-    else if (f.unique_key.n == 0) pre = 1;                            // gubernator.go:208-212 "field 'unique_key' cannot be empty"
-    else if (f.name.n == 0) pre = 2;                                  // gubernator.go:213-217 "field 'namespace' cannot be empty"
     else {
         const uint64_t kl = (uint64_t)f.name.n + 1 + f.unique_key.n;
         klen = kl > 0xffffffffull ? 0xffffffffu : (uint32_t)kl;
@@ -525,14 +526,22 @@ __global__ __launch_bounds__(256) void k_wire_fill(WireIn in, WireScratch sc, Wi
             for (uint32_t b = klen; b < ((klen + 7u) & ~7u); ++b) row[b] = 0;
         }
     }
+    const uint8_t flags = in.rpc_owner ? in.rpc_owner[r] : WIRE_RPC_OWNER;
+    // V1Instance.GetPeerRateLimits (gubernator.go:462-539) has no validation; the client RPC turns empty halves away and their row is never read
+    const bool peer = (flags & WIRE_RPC_PEER) != 0;
+    if (ok && !peer) {
+        if (f.unique_key.n == 0) { pre = 1; klen = 0; }               // gubernator.go:208-212 "field 'unique_key' cannot be empty"
+        else if (f.name.n == 0) { pre = 2; klen = 0; }                // gubernator.go:213-217 "field 'namespace' cannot be empty"
+    }
     out.key_len[i] = klen;
     out.pre_err[i] = pre;
     out.hits[i] = f.hits; out.limit[i] = f.limit; out.duration[i] = f.duration; out.burst[i] = f.burst;
     out.created_at[i] = f.created_at ? f.created_at : out.now_ms;      // gubernator.go:218-220
     out.algo_raw[i] = (int32_t)f.algorithm;
     out.algorithm[i] = (f.algorithm == 0 || f.algorithm == 1) ? (uint8_t)f.algorithm : 255;
-    out.behavior[i] = (uint32_t)f.behavior;
-    out.is_owner[i] = in.rpc_owner ? (in.rpc_owner[r] ? 1 : 0) : 1;
+    // a forwarded GLOBAL item drains: peers accumulate hits and may ask for more than remains (gubernator.go:506-512)
+    out.behavior[i] = (uint32_t)f.behavior | ((peer && ((uint32_t)f.behavior & 2u)) ? 32u : 0u);
+    out.is_owner[i] = flags ? 1 : 0;
 }
 
 // items of an RPC that a later record showed to be malformed (or that did not fit): dead slots — an empty key never reaches a bucket

@@ -59,8 +59,8 @@ inline void wpl_relax() {
 // long ones (an RPC with more than the cap is turned away whole and takes no place: gubernator.go:189-193).  Counting the records of EVERY
 // payload (a tag, a length and a skip per record: ~3 us for 1000) would keep stages full when long RPCs hold few, long requests, and was
 // measured on full ones: -3 ... -4 % at every caller count (profiles/r06_wire_pool.txt) — the bound of a long payload stays the cap.
-inline uint32_t wpl_item_bound(const uint8_t* p, size_t len, uint32_t cap) {
-    if (len >= GUBER_WPL_WALK_MAX) return (uint32_t)std::min<size_t>(cap, len / 2);
+// the top-level chain of a message walked: how many field-1 records it holds (exact when the message is well-formed)
+inline uint32_t wpl_count_records(const uint8_t* p, size_t len) {
     const uint8_t* end = p + len;
     uint32_t n = 0;
     while (p < end) {
@@ -78,7 +78,11 @@ inline uint32_t wpl_item_bound(const uint8_t* p, size_t len, uint32_t cap) {
             p += L;
         } else break;                                                  // (groups, reserved wire types: the decoders turn the payload away)
     }
-    return std::min(n, cap);
+    return n;
+}
+inline uint32_t wpl_item_bound(const uint8_t* p, size_t len, uint32_t cap) {
+    if (len >= GUBER_WPL_WALK_MAX) return (uint32_t)std::min<size_t>(cap, len / 2);
+    return std::min(wpl_count_records(p, len), cap);
 }
 // the CPUs this process may really use: the affinity mask, capped by the cgroup's quota (cpu.max) — a container on a 256-thread host with a
 // quota of 16 has 16
@@ -102,7 +106,7 @@ struct guber_wire_pool {
     struct Stage {
         guber_wire_dev* dec = nullptr;
         uint8_t* buf = nullptr;
-        PinBuf<uint32_t> meta; PinBuf<uint8_t> owner;                     // offs[R] | lens[R]; is_owner[R] — written by the callers at their index
+        PinBuf<uint32_t> meta; PinBuf<uint8_t> owner;                     // offs[R] | lens[R]; the RPCs' flag bytes (GUBER_WIRE_RPC_*)[R] — written by the callers at their index
         std::vector<int32_t> status; std::vector<uint32_t> first, count;  // per RPC, after the decode
         CohBuf<uint8_t> res; guber_result_t r{};                          // the raw answers in arrival order (host memory the device writes in place): of the RPCs the device does not encode
         CohBuf<uint8_t> enc; CohBuf<uint32_t> enc_len;                    // every RPC's GetRateLimitsResp bytes (k_wire_enc): at wire_enc_off(first, idx), enc_len[idx] of them
@@ -512,9 +516,18 @@ namespace {
 struct WplThreadBatch { guber_wire_batch_t* wb = nullptr; bool failed = false; ~WplThreadBatch() { if (wb) guber_wire_batch_destroy(wb); } };
 constexpr size_t WPL_DIRECT_MAX_BYTES = 2048;
 constexpr uint32_t WPL_DIRECT_ITEMS = 4;      // requests an RPC may hold to be evaluated by its caller (the per-request pool's GUBER_POOL_DIRECT_MAX)
+// the host transcoder in the RPC's mode (`flags`: GUBER_WIRE_RPC_*, the stage's per-RPC byte)
+inline int wpl_host_decode(guber_wire_batch_t* wb, const uint8_t* req, size_t len, uint32_t max_per_rpc, uint8_t flags, uint32_t* first, uint32_t* count) {
+    return (flags & GUBER_WIRE_RPC_PEER) ? guber_wire_decode_peer_requests(wb, req, len, max_per_rpc, first, count)
+                                         : guber_wire_decode_requests(wb, req, len, max_per_rpc, flags & GUBER_WIRE_RPC_OWNER, first, count);
+}
+inline int wpl_host_encode(const guber_wire_batch_t* wb, uint32_t count, uint8_t flags, int wrap_errors, uint8_t* resp, size_t cap, size_t* used) {
+    return (flags & GUBER_WIRE_RPC_PEER) ? guber_wire_encode_peer_responses(wb, 0, count, resp, cap, used)
+                                         : guber_wire_encode_responses(wb, 0, count, wrap_errors, resp, cap, used);
+}
 }
 // returns true when the call has been answered (rc, used); false: not for this path, nothing has happened
-static bool wpl_direct(guber_wire_pool* p, const uint8_t* req, size_t len, int is_owner, int wrap_errors, uint8_t* resp, size_t cap, size_t* used, int* rc_out) {
+static bool wpl_direct(guber_wire_pool* p, const uint8_t* req, size_t len, uint8_t flags, int wrap_errors, uint8_t* resp, size_t cap, size_t* used, int* rc_out) {
     thread_local WplThreadBatch tl;
     if (tl.failed) return false;
     if (!tl.wb) {
@@ -523,7 +536,7 @@ static bool wpl_direct(guber_wire_pool* p, const uint8_t* req, size_t len, int i
     }
     guber_wire_batch_reset(tl.wb, wpl_now_ms(p));
     uint32_t f0 = 0, c0 = 0;
-    int rc = guber_wire_decode_requests(tl.wb, req, len, p->max_per_rpc, is_owner ? 1 : 0, &f0, &c0);
+    int rc = wpl_host_decode(tl.wb, req, len, p->max_per_rpc, flags, &f0, &c0);
     if (rc == GUBER_E_WIRE_FULL || (rc == GUBER_OK && c0 > WPL_DIRECT_ITEMS)) return false;                  // (not what the bound promised: the stages take it)
     *used = 0;
     if (rc == GUBER_OK && c0 >= 1) {
@@ -560,7 +573,7 @@ static bool wpl_direct(guber_wire_pool* p, const uint8_t* req, size_t len, int i
             rc = guber_eval_batch(p->eng[eng[i]], &sv, &sr);
         }
         if (rc == GUBER_OK) {
-            rc = guber_wire_encode_responses(tl.wb, 0, c0, wrap_errors, resp, cap, used);
+            rc = wpl_host_encode(tl.wb, c0, flags, wrap_errors, resp, cap, used);
             if (rc == GUBER_E_NOMEM) fail(GUBER_E_NOMEM, "response buffer too small (the decisions HAVE been applied): guber_wire_pool_response_bound()");
         }
         p->st_items.fetch_add(c0, std::memory_order_relaxed);
@@ -586,9 +599,9 @@ extern "C" int guber_wire_pool_stats(guber_wire_pool_t* p, guber_wire_pool_stats
     return GUBER_OK;
 }
 
-// V1Instance.GetRateLimits / GetPeerRateLimits on the serialized messages (gubernator.go:183-306, :470-520 for the items this instance owns).
-extern "C" int guber_wire_pool_get_rate_limits(guber_wire_pool_t* p, const uint8_t* req, size_t len, int is_owner, int wrap_errors, uint8_t* resp, size_t cap,
-                                               size_t* resp_len) {
+// V1Instance.GetRateLimits / GetPeerRateLimits on the serialized messages (gubernator.go:183-306, :462-539 for the items this instance owns).
+// `flags`: GUBER_WIRE_RPC_* — the stage's per-RPC byte, which k_wire_fill reads.
+static int wpl_call(guber_wire_pool_t* p, const uint8_t* req, size_t len, uint8_t flags, int wrap_errors, uint8_t* resp, size_t cap, size_t* resp_len) {
     using WP = guber_wire_pool;
     if (!p || (!req && len) || !resp_len || (!resp && cap)) return fail(GUBER_E_INVALID_ARG, "null argument");
     *resp_len = 0;
@@ -600,7 +613,7 @@ extern "C" int guber_wire_pool_get_rate_limits(guber_wire_pool_t* p, const uint8
     struct Inside { std::atomic<uint32_t>& c; uint32_t n; explicit Inside(std::atomic<uint32_t>& x) : c(x), n(x.fetch_add(1, std::memory_order_relaxed) + 1) {} ~Inside() { c.fetch_sub(1, std::memory_order_relaxed); } } inside(p->inside);
     if (bound <= WPL_DIRECT_ITEMS && inside.n <= p->direct_max && len <= WPL_DIRECT_MAX_BYTES && !p->closed.load(std::memory_order_acquire)) {
         size_t used = 0; int rc = GUBER_OK;
-        if (wpl_direct(p, req, len, is_owner, wrap_errors, resp, cap, &used, &rc)) { *resp_len = used; return rc; }
+        if (wpl_direct(p, req, len, flags, wrap_errors, resp, cap, &used, &rc)) { *resp_len = used; return rc; }
     }
     // looking (spinning) is for callers that have a CPU to themselves: the pool's two threads need theirs, the others sleep at once
     const bool may_spin = p->spin_us && inside.n + 1 <= p->cpus / 2;
@@ -637,7 +650,7 @@ extern "C" int guber_wire_pool_get_rate_limits(guber_wire_pool_t* p, const uint8
     const size_t off = (size_t)wpl_b16(mine) * 16;
     if (idx == 0) { s.t_first_us.store(wpl_mono_us(), std::memory_order_relaxed); wpl_kick(p); }
     memcpy(s.buf + off, req, len);
-    s.meta.p[idx] = (uint32_t)off; s.meta.p[p->max_rpcs + idx] = (uint32_t)len; s.owner.p[idx] = is_owner ? 1 : 0;
+    s.meta.p[idx] = (uint32_t)off; s.meta.p[p->max_rpcs + idx] = (uint32_t)len; s.owner.p[idx] = flags;
     s.filled.fetch_add(1, std::memory_order_release);
     // ---- the stage's way through the GPU
     {
@@ -691,14 +704,14 @@ extern "C" int guber_wire_pool_get_rate_limits(guber_wire_pool_t* p, const uint8
                 if (!rc) {
                     guber_wire_batch_reset(wb, s.now_ms);
                     uint32_t f0 = 0, c0 = 0;
-                    rc = guber_wire_decode_requests(wb, req, len, p->max_per_rpc, is_owner ? 1 : 0, &f0, &c0);
+                    rc = wpl_host_decode(wb, req, len, p->max_per_rpc, flags, &f0, &c0);
                     if (!rc && c0 != count) rc = fail(GUBER_E_HIP, "guber_wire_pool: the device's and the host's decoders disagree about a payload");
                     if (!rc) {
                         guber_result_t* hr = guber_wire_batch_result(wb);
                         memcpy(hr->status, s.r.status + first, count); memcpy(hr->err, s.r.err + first, count);
                         memcpy(hr->limit, s.r.limit + first, (size_t)count * 8); memcpy(hr->remaining, s.r.remaining + first, (size_t)count * 8);
                         memcpy(hr->reset_time, s.r.reset_time + first, (size_t)count * 8);
-                        rc = guber_wire_encode_responses(wb, 0, count, wrap_errors, resp, cap, &used);
+                        rc = wpl_host_encode(wb, count, flags, wrap_errors, resp, cap, &used);
                         if (rc == GUBER_E_NOMEM) fail(GUBER_E_NOMEM, "response buffer too small (the decisions HAVE been applied): guber_wire_pool_response_bound()");
                     }
                     guber_wire_batch_destroy(wb);
@@ -711,4 +724,13 @@ extern "C" int guber_wire_pool_get_rate_limits(guber_wire_pool_t* p, const uint8
     s.readers.fetch_sub(1, std::memory_order_release);                // (the stage is not touched after this)
     *resp_len = used;
     return rc;
+}
+
+extern "C" int guber_wire_pool_get_rate_limits(guber_wire_pool_t* p, const uint8_t* req, size_t len, int is_owner, int wrap_errors, uint8_t* resp, size_t cap,
+                                               size_t* resp_len) {
+    return wpl_call(p, req, len, is_owner ? GUBER_WIRE_RPC_OWNER : 0, wrap_errors, resp, cap, resp_len);
+}
+// V1Instance.GetPeerRateLimits (gubernator.go:462-539): the same way through the pool with the peer bit in the RPC's byte
+extern "C" int guber_wire_pool_get_peer_rate_limits(guber_wire_pool_t* p, const uint8_t* req, size_t len, uint8_t* resp, size_t cap, size_t* resp_len) {
+    return wpl_call(p, req, len, GUBER_WIRE_RPC_OWNER | GUBER_WIRE_RPC_PEER, 0, resp, cap, resp_len);
 }

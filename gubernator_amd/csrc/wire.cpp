@@ -6,6 +6,7 @@
 //   gubernator.go:189-220                          batch cap, per-item validation, CreatedAt default
 //   client.go:39-41                                key = name + "_" + unique_key
 //   gubernator.go:250-255, workers.go:317-321      error texts of the evaluation
+//   gubernator.go:462-539, :600, workers.go:298-321 the peer RPC: no validation, DRAIN_OVER_LIMIT on GLOBAL items, its error texts
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -87,8 +88,13 @@ extern "C" void guber_wire_batch_reset(guber_wire_batch_t* b, int64_t now_ms) {
 
 extern "C" uint32_t guber_wire_batch_size(const guber_wire_batch_t* b) { return b ? b->n : 0; }
 
-extern "C" int guber_wire_decode_requests(guber_wire_batch_t* b, const uint8_t* msg, size_t len, uint32_t max_per_rpc,
-                                          uint8_t is_owner, uint32_t* first, uint32_t* count) {
+namespace {
+// One serialized GetRateLimitsReq / GetPeerRateLimitsReq appended to the batch.  `flags`: GUBER_WIRE_RPC_OWNER | GUBER_WIRE_RPC_PEER —
+// the peer RPC (V1Instance.GetPeerRateLimits, gubernator.go:462-539) has no per-item validation (every item gets its HashKey, empty
+// halves included), ORs DRAIN_OVER_LIMIT into GLOBAL items (:506-512) and evaluates as the owner (:486).
+int decode_requests(guber_wire_batch_t* b, const uint8_t* msg, size_t len, uint32_t max_per_rpc, uint8_t flags, uint32_t* first, uint32_t* count) {
+    const bool peer = (flags & GUBER_WIRE_RPC_PEER) != 0;
+    const uint8_t is_owner = (flags & (GUBER_WIRE_RPC_OWNER | GUBER_WIRE_RPC_PEER)) ? 1 : 0;
     if (!b || (!msg && len) || !first || !count) return GUBER_E_INVALID_ARG;
     *first = b->n; *count = 0;
     // One pass over the payload, writing straight into the SoA at [n0, ...): the batch's item / key counters are only
@@ -116,8 +122,10 @@ extern "C" int guber_wire_decode_requests(guber_wire_batch_t* b, const uint8_t* 
         p += v;
         if (full) { ++i; continue; }                                // keep validating and counting; nothing is stored any more
         uint8_t pre = GUBER_WIRE_PRE_OK;
-        if (f.unique_key.n == 0) pre = GUBER_WIRE_PRE_EMPTY_UNIQUE_KEY;          // gubernator.go:208-212
-        else if (f.name.n == 0) pre = GUBER_WIRE_PRE_EMPTY_NAME;                 // gubernator.go:213-217
+        if (!peer) {                                                             // (the client RPC's only: the peer RPC evaluates "name_", "_ukey", "_")
+            if (f.unique_key.n == 0) pre = GUBER_WIRE_PRE_EMPTY_UNIQUE_KEY;      // gubernator.go:208-212
+            else if (f.name.n == 0) pre = GUBER_WIRE_PRE_EMPTY_NAME;             // gubernator.go:213-217
+        }
         const uint64_t klen = pre == GUBER_WIRE_PRE_OK ? (uint64_t)f.name.n + 1 + f.unique_key.n : 0;
         if (i >= b->cap_items || klen > (uint64_t)(b->cap_keys - kused)) { full = true; ++i; continue; }
         b->pre_err[i] = pre;
@@ -132,7 +140,8 @@ extern "C" int guber_wire_decode_requests(guber_wire_batch_t* b, const uint8_t* 
         b->algo_raw[i] = (int32_t)f.algorithm;
         b->algorithm[i] = (f.algorithm == 0 || f.algorithm == 1) ? (uint8_t)f.algorithm : 255;
         b->behavior[i] = (uint32_t)f.behavior;
-        b->is_owner[i] = is_owner ? 1 : 0;
+        if (peer && (b->behavior[i] & GUBER_BEHAVIOR_GLOBAL)) b->behavior[i] |= GUBER_BEHAVIOR_DRAIN_OVER_LIMIT;   // gubernator.go:506-512
+        b->is_owner[i] = is_owner;
         b->greg_expire[i] = 0; b->greg_duration[i] = 0;
         if (pre == GUBER_WIRE_PRE_OK && ((uint32_t)f.behavior & GUBER_BEHAVIOR_DURATION_IS_GREGORIAN)) {   // interval.go:84-148 at clock.Now()
             any_greg = true;
@@ -150,6 +159,16 @@ extern "C" int guber_wire_decode_requests(guber_wire_batch_t* b, const uint8_t* 
     b->n = i; b->key_used = kused; b->any_greg = any_greg;
     memset(b->key_bytes + kused, 0, 16);
     return GUBER_OK;
+}
+}  // namespace
+
+extern "C" int guber_wire_decode_requests(guber_wire_batch_t* b, const uint8_t* msg, size_t len, uint32_t max_per_rpc,
+                                          uint8_t is_owner, uint32_t* first, uint32_t* count) {
+    return decode_requests(b, msg, len, max_per_rpc, is_owner ? GUBER_WIRE_RPC_OWNER : 0, first, count);
+}
+extern "C" int guber_wire_decode_peer_requests(guber_wire_batch_t* b, const uint8_t* msg, size_t len, uint32_t max_per_rpc,
+                                               uint32_t* first, uint32_t* count) {
+    return decode_requests(b, msg, len, max_per_rpc, GUBER_WIRE_RPC_OWNER | GUBER_WIRE_RPC_PEER, first, count);
 }
 
 extern "C" const guber_batch_t* guber_wire_batch_view(guber_wire_batch_t* b) {
@@ -178,7 +197,9 @@ extern "C" int guber_wire_eval(guber_engine_t* e, guber_wire_batch_t* b) {
 }
 
 namespace {
-// error text of item i ("" = none)
+enum { ERR_BARE = 0, ERR_CLIENT = 1, ERR_PEER = 2 };
+// error text of item i ("" = none).  ERR_CLIENT: gubernator.go:250-255; ERR_PEER: gubernator.go:523 around :600 around the worker's
+// text, which for an error out of an algorithm — here: the two Gregorian ones — is itself wrapped by workers.go:302-313
 std::string item_error(const guber_wire_batch* b, uint32_t i, int wrap) {
     if (b->pre_err[i] == GUBER_WIRE_PRE_EMPTY_UNIQUE_KEY) return "field 'unique_key' cannot be empty";
     if (b->pre_err[i] == GUBER_WIRE_PRE_EMPTY_NAME) return "field 'namespace' cannot be empty";
@@ -187,7 +208,13 @@ std::string item_error(const guber_wire_batch* b, uint32_t i, int wrap) {
     char buf[256];
     if (code == GUBER_ITEM_E_INVALID_ALGORITHM) snprintf(buf, sizeof buf, guber_item_strerror(code), (int)b->algo_raw[i]);   // workers.go:318
     else snprintf(buf, sizeof buf, "%s", guber_item_strerror(code));
-    if (!wrap) return buf;
+    if (wrap == ERR_BARE) return buf;
+    if (wrap == ERR_PEER) {
+        std::string s = "Error in getLocalRateLimit: during workerPool.GetRateLimit: ";
+        if (code == GUBER_ITEM_E_GREGORIAN_WEEKS || code == GUBER_ITEM_E_GREGORIAN_INVALID)
+            s += b->algorithm[i] == GUBER_ALGO_LEAKY_BUCKET ? "Error in leakyBucket: " : "Error in tokenBucket: ";
+        return s + buf;
+    }
     std::string s = "Error while apply rate limit for '";                                                                     // gubernator.go:250-255
     s.append((const char*)b->key_bytes + b->key_off[i], b->key_off[i + 1] - b->key_off[i]);
     s += "': "; s += buf;
@@ -211,14 +238,15 @@ inline RespFields resp_fields(const guber_wire_batch* b, uint32_t i, bool has_er
 
 extern "C" size_t guber_wire_encode_bound(const guber_wire_batch_t* b, uint32_t first, uint32_t count) {
     if (!b || first > b->n || count > b->n - first) return 0;
-    // tag + length (<= 3) + 4 varint fields (<= 11 each) + error field: wrapper text + key + message (<= 256)
+    // tag + length (<= 3) + 4 varint fields (<= 11 each) + error field: wrapper text + key + message (<= 256).  (The peer RPC's wrappers,
+    // 82 bytes and no key, around a message of at most 92 lie inside the 40 + 256 as well.)
     size_t bound = 0;
     for (uint32_t i = first; i < first + count; ++i) bound += 4 + 44 + 3 + 40 + 256 + (b->key_off[i + 1] - b->key_off[i]);
     return bound;
 }
 
-extern "C" int guber_wire_encode_responses(const guber_wire_batch_t* b, uint32_t first, uint32_t count, int wrap_errors,
-                                           uint8_t* out, size_t cap, size_t* len) {
+namespace {
+int encode_responses(const guber_wire_batch_t* b, uint32_t first, uint32_t count, int wrap_errors, uint8_t* out, size_t cap, size_t* len) {
     if (!b || !len || (!out && cap) || first > b->n || count > b->n - first) return GUBER_E_INVALID_ARG;
     size_t used = 0;
     bool overflow = false;
@@ -244,6 +272,15 @@ extern "C" int guber_wire_encode_responses(const guber_wire_batch_t* b, uint32_t
     }
     *len = used;
     return overflow ? GUBER_E_NOMEM : GUBER_OK;
+}
+}  // namespace
+
+extern "C" int guber_wire_encode_responses(const guber_wire_batch_t* b, uint32_t first, uint32_t count, int wrap_errors,
+                                           uint8_t* out, size_t cap, size_t* len) {
+    return encode_responses(b, first, count, wrap_errors ? ERR_CLIENT : ERR_BARE, out, cap, len);
+}
+extern "C" int guber_wire_encode_peer_responses(const guber_wire_batch_t* b, uint32_t first, uint32_t count, uint8_t* out, size_t cap, size_t* len) {
+    return encode_responses(b, first, count, ERR_PEER, out, cap, len);
 }
 
 // ---- UpdatePeerGlobals ---------------------------------------------------------------------------------------------

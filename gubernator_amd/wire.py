@@ -9,16 +9,18 @@ from . import GuberError, lib
 from .abi import GuberBatch, GuberResult
 
 E_WIRE_MALFORMED, E_WIRE_TOO_LARGE, E_WIRE_FULL = -20, -21, -22
+RPC_OWNER, RPC_PEER = 1, 2            # GUBER_WIRE_RPC_*: the per-RPC flag byte of the device decoder and the payload stage
 WIRE_SYMBOLS = [
     "guber_wire_batch_create", "guber_wire_batch_destroy", "guber_wire_batch_reset", "guber_wire_batch_size",
-    "guber_wire_decode_requests", "guber_wire_batch_view", "guber_wire_batch_result", "guber_wire_batch_pre_errors",
-    "guber_wire_eval", "guber_wire_encode_bound", "guber_wire_encode_responses",
+    "guber_wire_decode_requests", "guber_wire_decode_peer_requests", "guber_wire_batch_view", "guber_wire_batch_result", "guber_wire_batch_pre_errors",
+    "guber_wire_eval", "guber_wire_encode_bound", "guber_wire_encode_responses", "guber_wire_encode_peer_responses",
     "guber_wire_items_create", "guber_wire_items_destroy", "guber_wire_decode_globals", "guber_wire_encode_globals",
     "guber_wire_dev_create", "guber_wire_dev_destroy", "guber_wire_dev_decode", "guber_wire_dev_buffer", "guber_wire_dev_decode_staged",
     "guber_wire_dev_eval", "guber_wire_dev_eval_front", "guber_wire_dev_columns",
     "guber_wire_dev_set_stream", "guber_wire_dev_decode_staged_async", "guber_wire_dev_decode_collect", "guber_wire_dev_eval_front_async",
     "guber_wire_dev_eval_collect", "guber_wire_dev_route_front_async", "guber_wire_dev_route_ready",
     "guber_wire_pool_create", "guber_wire_pool_destroy", "guber_wire_pool_get_rate_limits", "guber_wire_pool_response_bound",
+    "guber_wire_pool_get_peer_rate_limits", "guber_wire_pool_update_peer_globals",
     "guber_wire_pool_set_clock", "guber_wire_pool_stats",
 ]
 _bound = False
@@ -37,6 +39,9 @@ def _lib():
         L.guber_wire_batch_size.restype = C.c_uint32
         L.guber_wire_decode_requests.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint8,
                                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.guber_wire_decode_peer_requests.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32,
+                                                      C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.guber_wire_encode_peer_responses.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.guber_wire_batch_view.argtypes = [C.c_void_p]
         L.guber_wire_batch_view.restype = C.POINTER(GuberBatch)
         L.guber_wire_batch_result.argtypes = [C.c_void_p]
@@ -85,12 +90,16 @@ class WireBatch:
     def __len__(self):
         return self.L.guber_wire_batch_size(self.h)
 
-    def decode(self, payload: bytes, max_per_rpc=0, is_owner=True):
+    def decode(self, payload: bytes, max_per_rpc=0, is_owner=True, peer=False):
         """Append one serialized request message; returns (first, count).  Raises GuberError with the code
-        E_WIRE_MALFORMED / E_WIRE_TOO_LARGE / E_WIRE_FULL (nothing appended)."""
+        E_WIRE_MALFORMED / E_WIRE_TOO_LARGE / E_WIRE_FULL (nothing appended).  peer=True: as V1Instance.GetPeerRateLimits takes a
+        GetPeerRateLimitsReq (no validation, DRAIN_OVER_LIMIT on GLOBAL items, owner)."""
         first, count = C.c_uint32(), C.c_uint32()
-        rc = self.L.guber_wire_decode_requests(self.h, payload, len(payload), max_per_rpc, 1 if is_owner else 0,
-                                               C.byref(first), C.byref(count))
+        if peer:
+            rc = self.L.guber_wire_decode_peer_requests(self.h, payload, len(payload), max_per_rpc, C.byref(first), C.byref(count))
+        else:
+            rc = self.L.guber_wire_decode_requests(self.h, payload, len(payload), max_per_rpc, 1 if is_owner else 0,
+                                                   C.byref(first), C.byref(count))
         if rc:
             raise GuberError(rc, self.L.guber_strerror(rc).decode())
         return first.value, count.value
@@ -125,11 +134,15 @@ class WireBatch:
         if rc:
             raise GuberError(rc, self.L.guber_strerror(rc).decode())
 
-    def encode(self, first, count, wrap_errors=True):
+    def encode(self, first, count, wrap_errors=True, peer=False):
+        """peer=True: GetPeerRateLimitsResp with the peer RPC's error texts (guber_wire_encode_peer_responses)"""
         cap = self.L.guber_wire_encode_bound(self.h, first, count)
         buf = (C.c_uint8 * max(cap, 1))()
         n = C.c_size_t()
-        rc = self.L.guber_wire_encode_responses(self.h, first, count, 1 if wrap_errors else 0, buf, cap, C.byref(n))
+        if peer:
+            rc = self.L.guber_wire_encode_peer_responses(self.h, first, count, buf, cap, C.byref(n))
+        else:
+            rc = self.L.guber_wire_encode_responses(self.h, first, count, 1 if wrap_errors else 0, buf, cap, C.byref(n))
         if rc:
             raise GuberError(rc, self.L.guber_strerror(rc).decode())
         return bytes(buf[:n.value])
@@ -303,12 +316,15 @@ class WirePool:
     (gubernator.go:183-306).  get_rate_limits() is what one gRPC handler thread calls; it may be called from many threads at once
     (the call releases the GIL)."""
 
-    def __init__(self, engines, placement=None, **cfg):
+    def __init__(self, engines, placement=None, global_engine=-1, **cfg):
+        """global_engine: index of the engine that keeps GLOBAL state (guber_route_rule_t.global_engine), -1 = none"""
         L = self.L = _lib()
         L.guber_wire_pool_create.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.POINTER(WirePoolConfig), C.POINTER(C.c_void_p)]
         L.guber_wire_pool_destroy.argtypes = [C.c_void_p]
         L.guber_wire_pool_destroy.restype = None
         L.guber_wire_pool_get_rate_limits.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.guber_wire_pool_get_peer_rate_limits.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.guber_wire_pool_update_peer_globals.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32)]
         L.guber_wire_pool_response_bound.argtypes = [C.c_char_p, C.c_size_t]
         L.guber_wire_pool_response_bound.restype = C.c_size_t
         L.guber_wire_pool_set_clock.argtypes = [C.c_void_p, C.c_int64]
@@ -316,7 +332,7 @@ class WirePool:
         self.engines = list(engines)
         self.placement = placement
         hs = (C.c_void_p * len(self.engines))(*[e.h for e in self.engines])
-        rule = placement.export() if placement is not None else None
+        rule = placement.export(global_engine=global_engine) if placement is not None else None
         c = WirePoolConfig(**cfg)
         self.h = C.c_void_p()
         rc = L.guber_wire_pool_create(hs, len(self.engines), C.byref(rule) if rule is not None else None, C.byref(c), C.byref(self.h))
@@ -335,6 +351,25 @@ class WirePool:
         if rc:
             raise GuberError(rc, lib().guber_last_error().decode())
         return buf.raw[:n.value]
+
+    def get_peer_rate_limits(self, payload, cap=None):
+        """serialized GetPeerRateLimitsReq -> serialized GetPeerRateLimitsResp, as V1Instance.GetPeerRateLimits answers it (gubernator.go:462-539)"""
+        cap = self.L.guber_wire_pool_response_bound(payload, len(payload)) if cap is None else cap
+        buf = C.create_string_buffer(max(cap, 1))
+        n = C.c_size_t(0)
+        rc = self.L.guber_wire_pool_get_peer_rate_limits(self.h, payload, len(payload), buf, cap, C.byref(n))
+        if rc:
+            raise GuberError(rc, lib().guber_last_error().decode())
+        return buf.raw[:n.value]
+
+    def update_peer_globals(self, payload):
+        """serialized UpdatePeerGlobalsReq -> the number of items installed (gubernator.go:425-459); GuberError when the message is turned
+        away whole (nothing installed)"""
+        n = C.c_uint32(0)
+        rc = self.L.guber_wire_pool_update_peer_globals(self.h, payload, len(payload), C.byref(n))
+        if rc:
+            raise GuberError(rc, lib().guber_last_error().decode())
+        return n.value
 
     def stats(self):
         st = WirePoolStats()

@@ -48,6 +48,15 @@ extern "C" {
 #define GUBER_WIRE_PRE_EMPTY_UNIQUE_KEY 1   /* "field 'unique_key' cannot be empty" */
 #define GUBER_WIRE_PRE_EMPTY_NAME 2         /* "field 'namespace' cannot be empty" */
 
+/* what a request message is, one byte per RPC: the per-RPC byte of the device decoder (guber_wire_dev_decode*'s is_owner[]) and of the
+ * payload stage.  Bit 0: RateLimitReqState.IsOwner of its items.  Bit 1: the message is a GetPeerRateLimitsReq and is served as
+ * V1Instance.GetPeerRateLimits serves it (gubernator.go:462-539) — no per-item validation (an item with an empty name or unique_key is
+ * evaluated on the key name + "_" + unique_key, client.go:39), Behavior_DRAIN_OVER_LIMIT ORed into every item that carries Behavior_GLOBAL
+ * (:506-512: peers accumulate hits and may ask for more than remains), items evaluated as the owner (:486: the peer bit implies the owner
+ * bit).  0 and 1 mean what they always meant. */
+#define GUBER_WIRE_RPC_OWNER 1u
+#define GUBER_WIRE_RPC_PEER 2u
+
 typedef struct guber_wire_batch guber_wire_batch_t;
 
 /* A growable-up-to-capacity SoA batch plus the result arrays of its evaluation. */
@@ -68,6 +77,13 @@ uint32_t guber_wire_batch_size(const guber_wire_batch_t* b);
 int guber_wire_decode_requests(guber_wire_batch_t* b, const uint8_t* msg, size_t len, uint32_t max_per_rpc,
                                uint8_t is_owner, uint32_t* first, uint32_t* count);
 
+/* The same for one GetPeerRateLimitsReq served as the reference's peer RPC serves it (GUBER_WIRE_RPC_PEER above): every item gets its key
+ * ("name_", "_ukey" or "_" when a half is empty) and no validation code, GLOBAL items get DRAIN_OVER_LIMIT, is_owner = 1; the CreatedAt
+ * default (gubernator.go:514-518) and max_per_rpc are as above — GUBER_E_WIRE_TOO_LARGE is the same code, the caller picks the text
+ * ("'PeerRequest.rate_limits' list too large; max size is '1000'", gubernator.go:465). */
+int guber_wire_decode_peer_requests(guber_wire_batch_t* b, const uint8_t* msg, size_t len, uint32_t max_per_rpc,
+                                    uint32_t* first, uint32_t* count);
+
 /* The SoA view to hand to guber_eval_batch (valid until the next reset / decode), the result arrays an
  * evaluation fills, and the per-item validation codes. */
 const guber_batch_t* guber_wire_batch_view(guber_wire_batch_t* b);
@@ -84,6 +100,12 @@ int guber_wire_eval(guber_engine_t* e, guber_wire_batch_t* b);
 size_t guber_wire_encode_bound(const guber_wire_batch_t* b, uint32_t first, uint32_t count);
 int guber_wire_encode_responses(const guber_wire_batch_t* b, uint32_t first, uint32_t count, int wrap_errors,
                                 uint8_t* out, size_t cap, size_t* len);
+
+/* The same as GetPeerRateLimitsResp with the peer RPC's error texts: an item's error is wrapped as "Error in getLocalRateLimit: "
+ * (gubernator.go:523) around "during workerPool.GetRateLimit: " (:600) around the worker's text; the two Gregorian errors, which come out
+ * of an algorithm, carry "Error in tokenBucket: " / "Error in leakyBucket: " (workers.go:302-313) in front of theirs.  The engine's own
+ * errors (table full, key too long), which the reference does not have, get the two outer wrappers.  guber_wire_encode_bound covers it. */
+int guber_wire_encode_peer_responses(const guber_wire_batch_t* b, uint32_t first, uint32_t count, uint8_t* out, size_t cap, size_t* len);
 
 /* ---- UpdatePeerGlobals (peers.proto:51-63; sender global.go:234-283 broadcastPeers, receiver gubernator.go:425-459) ----
  * The third payload kind that touches the path: the owner of GLOBAL keys broadcasts their state, every other peer
@@ -116,7 +138,9 @@ int guber_wire_encode_globals(const uint8_t* key_bytes, const uint32_t* key_off,
  *      arrays the engine's kernels read.
  *   guber_wire_dev_create   a decoder bound to an engine: at most max_items items, max_payload_bytes payload bytes and max_rpcs
  *                           payloads per decode (max_items <= the engine's max_batch; an RPC holds at most min(max_items, 4096) items)
- *   guber_wire_dev_decode   nrpc payloads (msgs[r], lens[r]; is_owner[r] = RateLimitReqState.IsOwner of its items, NULL = all owner;
+ *   guber_wire_dev_decode   nrpc payloads (msgs[r], lens[r]; is_owner[r] = RateLimitReqState.IsOwner of its items, NULL = all owner —
+ *                           the byte is the flag byte above: GUBER_WIRE_RPC_OWNER | GUBER_WIRE_RPC_PEER decodes payload r as the peer RPC
+ *                           does, in k_wire_fill, from the byte it loads anyway; guber_wire_dev_decode_staged[_async] alike;
  *                           max_per_rpc as guber_wire_decode_requests) -> per RPC: status[r] (GUBER_OK, GUBER_E_WIRE_MALFORMED,
  *                           GUBER_E_WIRE_TOO_LARGE), first[r], count[r] = the slice of the batch its items occupy (responses are
  *                           positionally aligned); *n_items = the batch size.  Items of a rejected RPC that were already placed stay
@@ -188,6 +212,20 @@ int guber_wire_dev_route_ready(guber_wire_dev_t* d, guber_front_t* f);
  *                                     GUBER_E_WIRE_MALFORMED / GUBER_E_WIRE_TOO_LARGE: the message is turned away whole (nothing of it evaluated),
  *                                     as the protobuf runtime / gubernator.go:189-193 do.  The bytes equal guber_wire_encode_responses' (and the
  *                                     protobuf runtimes').
+ *   guber_wire_pool_get_peer_rate_limits  req/len: one serialized GetPeerRateLimitsReq, answered as V1Instance.GetPeerRateLimits answers it
+ *                                     (gubernator.go:462-539; GUBER_WIRE_RPC_PEER above: no validation, DRAIN_OVER_LIMIT on GLOBAL items, the peer
+ *                                     RPC's error texts).  Everything else — stages, the caller's own evaluation of a small RPC, routing of GLOBAL items
+ *                                     to the GLOBAL engine and its update queue, buffers, codes — as guber_wire_pool_get_rate_limits; for
+ *                                     GUBER_E_WIRE_TOO_LARGE the caller answers "'PeerRequest.rate_limits' list too large; max size is '1000'" (:465).
+ *   guber_wire_pool_update_peer_globals   msg/len: one serialized UpdatePeerGlobalsReq (gubernator.go:425-459).  Decoded by guber_wire_decode_globals at
+ *                                     the pool's clock; every item goes to the engine the pool's rule keeps GLOBAL state in — the GLOBAL engine when
+ *                                     the rule has one, else the table XXH64 of the key picks, as for a GLOBAL request — and is installed there by ONE
+ *                                     guber_add_items per engine touched (LRUCache.Add, item by item in the message's order).  Safe beside stages in
+ *                                     flight and callers evaluating their own RPCs: guber_add_items takes the engine's lock, as every evaluation
+ *                                     does.  *installed (may be NULL) = the items installed.  A malformed message (GUBER_E_WIRE_MALFORMED), or one with
+ *                                     an item no table can hold (an empty key: GUBER_E_INVALID_ARG; a key longer than max_key_bytes:
+ *                                     GUBER_E_KEY_TOO_LONG), is turned away whole: nothing is installed.  The decode stays on the HOST on purpose: a
+ *                                     broadcast holds at most 1000 items per sync interval (global.go:234-283, GlobalBatchLimit), microseconds of work.
  *   guber_wire_pool_set_clock         0 = the wall clock (clock.Now(): a stage's items share the instant it was sealed); otherwise a frozen clock
  *                                     in ms, as the reference's tests use clock.Freeze
  *   What this surface does NOT do: the Store's write-through callbacks (store.go:49-65: guber_pool_set_store / guber_eval_batch_store — a daemon
@@ -219,6 +257,8 @@ int guber_wire_pool_create(guber_engine_t* const* engines, uint32_t n_engines, c
 void guber_wire_pool_destroy(guber_wire_pool_t* p);     /* no call may be in flight or arrive any more */
 int guber_wire_pool_get_rate_limits(guber_wire_pool_t* p, const uint8_t* req, size_t len, int is_owner, int wrap_errors, uint8_t* resp, size_t cap,
                                     size_t* resp_len);
+int guber_wire_pool_get_peer_rate_limits(guber_wire_pool_t* p, const uint8_t* req, size_t len, uint8_t* resp, size_t cap, size_t* resp_len);
+int guber_wire_pool_update_peer_globals(guber_wire_pool_t* p, const uint8_t* msg, size_t len, uint32_t* installed);
 size_t guber_wire_pool_response_bound(const uint8_t* req, size_t len);
 int guber_wire_pool_set_clock(guber_wire_pool_t* p, int64_t now_ms);
 int guber_wire_pool_stats(guber_wire_pool_t* p, guber_wire_pool_stats_t* out);

@@ -1,5 +1,6 @@
 // engine_batch.inl — part of guber_engine.hip's translation unit (included there, in this order; not a header of its own):
-// the bounded cache's pre-pass (lru_admit), a batch's prelude and plans, launch_batch and the device-pointer entry points of ONE engine.
+// the bounded cache's pre-pass (lru_admit), a batch's prelude and plans, PairGroup (the ONE place that plans and launches the two-launch
+// pipeline, for one table or a group), launch_batch and the device-pointer entry points of ONE engine.
 // ---- the bounded cache's exact victim order (guber_kernels_lru.h) --------------------------------------------------------------
 // May this call make the cache longer than cache_size?  size_upper is the host's upper bound of the live items (every request
 // might create one); lru_admit reads the exact figure when it matters.
@@ -235,6 +236,75 @@ static void finish_fast(guber_engine* e, uint32_t n) {
     e->batches++;
 }
 
+// The two-launch pipeline (k_front -> k_eval2) for one table, or for several tables of ONE device and stream in one pair of launches.
+// add() runs a table's prelude and plan and appends its arguments to the block the group was made over: a FrontArgs / EvalArgs pair
+// (one table), a MultiFront / MultiEval pair that travels by value (<= MULTI_MAX tables) or a MultiArgsMem in device-visible host memory
+// (<= MULTI_MEM_MAX; the CALLER brings it to its place in HBM ahead of launch(): a copy command, a segment of its copy kernel).  After
+// an error from add(): launch what is planned, then report.  The engines' mutexes are the caller's.
+struct PairGroup {
+    enum Form { SINGLE, MULTI, MULTI_MEM };                        // k_front / k_eval2, the _multi forms, the _multi_mem forms
+    FrontArgs* fsub; EvalArgs* esub; uint32_t *fend = nullptr, *eend = nullptr, *fnb = nullptr, *enb = nullptr; int cap = 1;
+    MultiFront* MF = nullptr; MultiEval* ME = nullptr; MultiArgsMem* DA = nullptr;
+    guber_engine* eng[MULTI_MEM_MAX]; uint32_t ns[MULTI_MEM_MAX];
+    int planned = 0; uint32_t tiles = 0; uint64_t units = 0;
+    guber_engine* timer = nullptr;                                 // who keeps the per-kernel timing, when enabled: the first table's engine unless the caller names one
+    PairGroup(FrontArgs& F, EvalArgs& E) : fsub(&F), esub(&E) {}
+    PairGroup(MultiFront& F, MultiEval& E) : MF(&F), ME(&E) { over(F, E); }
+    PairGroup(MultiArgsMem* host, MultiArgsMem* dev) : DA(dev) { over(host->F, host->E); }
+    template <typename F_, typename E_> void over(F_& F, E_& E) {
+        fsub = F.sub; esub = E.sub; fend = F.end_tile; eend = E.end_tile; fnb = &F.nb; enb = &E.nb; cap = (int)(sizeof(F.sub) / sizeof(F.sub[0]));
+        *fnb = *enb = 0;
+    }
+    int add(guber_engine* e, const BatchView& B, const ResultView& R, bool host_resident) {
+        if (planned == cap) return fail(GUBER_E_INVALID_ARG, "more tables than the launch's argument block holds");
+        Work W; FastPlan P;
+        int rc = batch_prelude(e, B, W);
+        if (!rc) rc = plan_fast(e, B, host_resident, W, P);
+        if (rc) return rc;
+        tiles += P.ftiles; units += B.n;
+        fsub[planned] = FrontArgs{e->T, P.B2, P.W};
+        esub[planned] = EvalArgs{e->T, P.B3, R, P.W};
+        eng[planned] = e; ns[planned] = B.n;
+        ++planned;
+        if (fend) { fend[planned - 1] = eend[planned - 1] = tiles; *fnb = *enb = (uint32_t)planned; }
+        return 0;
+    }
+    // the pair on the tables' stream in the form the caller names, then every table's finish_fast; fused: the tables count as fused_batches
+    int launch(Form form, bool fused) {
+        if (!planned) return 0;
+        if (form == SINGLE ? planned != 1 : form == MULTI ? !MF : !DA) return fail(GUBER_E_INVALID_ARG, "the group was not planned for this form of launch");
+        static_assert(FT == 256, "k_eval2's workgroup is k_front's tile");
+        guber_engine* e0 = timer ? timer : eng[0];
+        hipStream_t st = e0->stream;
+        e0->span_begin(form == SINGLE ? KT_FRONT : KT_FRONT_MULTI, units);
+        if (form == SINGLE) hipLaunchKernelGGL(k_front, dim3(tiles), dim3(FT), 0, st, fsub[0].T, fsub[0].B, fsub[0].W);
+        else if (form == MULTI) hipLaunchKernelGGL(k_front_multi, dim3(tiles), dim3(FT), 0, st, *MF);
+        else hipLaunchKernelGGL(k_front_multi_mem, dim3(tiles), dim3(FT), 0, st, (const MultiFrontMem*)&DA->F);
+        e0->span_end();
+        e0->span_begin(form == SINGLE ? KT_EVAL2 : KT_EVAL2_MULTI, units);
+        if (form == SINGLE) hipLaunchKernelGGL(k_eval2, dim3(tiles), dim3(256), 0, st, esub[0]);
+        else if (form == MULTI) hipLaunchKernelGGL(k_eval2_multi, dim3(tiles), dim3(256), 0, st, *ME);
+        else hipLaunchKernelGGL(k_eval2_multi_mem, dim3(tiles), dim3(256), 0, st, (const MultiEvalMem*)&DA->E);
+        e0->span_end();
+        const bool launched = hipGetLastError() == hipSuccess;
+        for (int i = 0; i < planned; ++i) { finish_fast(eng[i], ns[i]); if (fused) eng[i]->fused_batches++; }
+        return launched ? 0 : fail(GUBER_E_HIP, "kernel launch");
+    }
+};
+// the 16-byte pieces of a MultiArgsMem that carry `planned` tables' arguments (what a copy kernel brings over): F's head and sub[0 .. planned), E's
+static void margs_segments(int planned, uint32_t* off16, uint32_t* n16) {
+    off16[0] = 0; n16[0] = (uint32_t)((offsetof(MultiFrontMem, sub) + (size_t)planned * sizeof(FrontArgs) + 15) / 16);
+    off16[1] = (uint32_t)(offsetof(MultiArgsMem, E) / 16); n16[1] = (uint32_t)((offsetof(MultiEvalMem, sub) + (size_t)planned * sizeof(EvalArgs) + 15) / 16);
+}
+
+// a caller's guber_batch_t / guber_result_t as the kernels' views; the per-batch aggregates of a result start at zero
+static BatchView view_of(const guber_batch_t& b) {
+    return BatchView{b.n, 0, b.key_bytes, b.key_off, b.hits, b.limit, b.duration, b.burst, b.created_at,
+                     b.algorithm, b.behavior, b.is_owner, b.greg_expire, b.greg_duration, b.now_ms};
+}
+static ResultView view_of(guber_result_t& r) { return ResultView{r.status, r.limit, r.remaining, r.reset_time, r.err}; }
+static void clear_aggregates(guber_result_t& r) { r.over_limit_count = r.cache_hits = r.cache_misses = r.unexpired_evictions = 0; r.cache_size = 0; }
+
 static int launch_batch_inner(guber_engine* e, const BatchView& B, const ResultView& R, bool host_resident);
 // requests [pos, pos + len) of a batch as a batch of their own
 static BatchView batch_slice(const BatchView& B, uint32_t pos, uint32_t len) {
@@ -286,13 +356,42 @@ static int launch_batch(guber_engine* e, const BatchView& B, const ResultView& R
 static int launch_batch_inner(guber_engine* e, const BatchView& B, const ResultView& R, bool host_resident) {
     const uint32_t n = B.n;
     if (n == 0) return 0;
+    const bool part = takes_part_path(e, n, host_resident, false);
+    if (!part && takes_fast_path(e, n)) {
+        // two launches: resolve + in-tile grouping, then evaluation
+        FrontArgs FA; EvalArgs EA;
+        PairGroup pg(FA, EA);
+        int rc = pg.add(e, B, R, host_resident);
+        if (!rc) rc = pg.launch(PairGroup::SINGLE, false);
+        if (rc) return rc;
+#ifdef GUBER_PHASE_TIMING
+        if (n == e->fast_cap) {   // fold the stamps of full batches: avg and max over workgroups, relative to the first workgroup's entry
+            static unsigned long long hb[4096];
+            (void)hipStreamSynchronize(e->stream);
+            (void)hipMemcpy(hb, e->dbg.p, sizeof(hb), hipMemcpyDeviceToHost);
+            for (int kern = 0; kern < 2; ++kern) {
+                const int ns = kern ? 5 : 8;
+                const unsigned long long* b = hb + kern * 2048;
+                unsigned long long t0 = ~0ull;
+                for (uint32_t t = 0; t < pg.tiles; ++t) t0 = b[t * 8] < t0 ? b[t * 8] : t0;
+                for (int k = 0; k < ns; ++k) {
+                    double sum = 0, mx = 0;
+                    for (uint32_t t = 0; t < pg.tiles; ++t) { const double v = (double)(b[t * 8 + k] - t0) * 0.01; sum += v; mx = v > mx ? v : mx; }
+                    e->dbg_avg[kern][k] += sum / pg.tiles; e->dbg_max[kern][k] += mx;
+                }
+            }
+            e->dbg_n++;
+        }
+#endif
+        return 0;
+    }
     Work W;
     {
         const int rc = batch_prelude(e, B, W);
         if (rc) return rc;
     }
     const uint32_t tiles = W.tiles;
-    if (takes_part_path(e, n, host_resident, false)) {
+    if (part) {
         FastPlan P;
         {
             const int rc = plan_part(e, B, W, P);
@@ -330,43 +429,6 @@ static int launch_batch_inner(guber_engine* e, const BatchView& B, const ResultV
         }
 #endif
         e->batches++; e->part_batches++;
-        return 0;
-    }
-    if (takes_fast_path(e, n)) {
-        // two launches: resolve + in-tile grouping, then evaluation
-        FastPlan P;
-        {
-            const int rc = plan_fast(e, B, host_resident, W, P);
-            if (rc) return rc;
-        }
-        const uint32_t ftiles = P.ftiles;
-        e->span_begin(KT_FRONT, n);
-        hipLaunchKernelGGL(k_front, dim3(ftiles), dim3(FT), 0, e->stream, e->T, P.B2, P.W);
-        e->span_end();
-        e->span_begin(KT_EVAL2, n);
-        hipLaunchKernelGGL(k_eval2, dim3((n + 255) / 256), dim3(256), 0, e->stream, EvalArgs{e->T, P.B3, R, P.W});
-        e->span_end();
-        HIPCHK(hipGetLastError());
-#ifdef GUBER_PHASE_TIMING
-        if (n == e->fast_cap) {   // fold the stamps of full batches: avg and max over workgroups, relative to the first workgroup's entry
-            static unsigned long long hb[4096];
-            (void)hipStreamSynchronize(e->stream);
-            (void)hipMemcpy(hb, e->dbg.p, sizeof(hb), hipMemcpyDeviceToHost);
-            for (int kern = 0; kern < 2; ++kern) {
-                const int ns = kern ? 5 : 8;
-                const unsigned long long* b = hb + kern * 2048;
-                unsigned long long t0 = ~0ull;
-                for (uint32_t t = 0; t < ftiles; ++t) t0 = b[t * 8] < t0 ? b[t * 8] : t0;
-                for (int k = 0; k < ns; ++k) {
-                    double sum = 0, mx = 0;
-                    for (uint32_t t = 0; t < ftiles; ++t) { const double v = (double)(b[t * 8 + k] - t0) * 0.01; sum += v; mx = v > mx ? v : mx; }
-                    e->dbg_avg[kern][k] += sum / ftiles; e->dbg_max[kern][k] += mx;
-                }
-            }
-            e->dbg_n++;
-        }
-#endif
-        finish_fast(e, n);
         return 0;
     }
     int passes = 1;
@@ -416,11 +478,8 @@ extern "C" int guber_eval_batch_dev(guber_engine_t* e, const guber_batch_t* b, g
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(e->mu);
     if (e->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
-    BatchView B{b->n, 0, b->key_bytes, b->key_off, b->hits, b->limit, b->duration, b->burst, b->created_at,
-                b->algorithm, b->behavior, b->is_owner, b->greg_expire, b->greg_duration, b->now_ms};
-    ResultView R{r->status, r->limit, r->remaining, r->reset_time, r->err};
-    r->over_limit_count = r->cache_hits = r->cache_misses = r->unexpired_evictions = 0; r->cache_size = 0;
-    return launch_batch(e, B, R);
+    clear_aggregates(*r);
+    return launch_batch(e, view_of(*b), view_of(*r));
 }
 
 extern "C" int guber_eval_batches_dev(guber_engine_t* e, const guber_batch_t* batches, guber_result_t* results, uint32_t count,
@@ -434,12 +493,8 @@ extern "C" int guber_eval_batches_dev(guber_engine_t* e, const guber_batch_t* ba
     std::lock_guard<std::mutex> lk(e->mu);
     if (e->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
     for (uint32_t k = 0; k < count; ++k) {
-        const guber_batch_t* b = &batches[k]; guber_result_t* r = &results[k];
-        BatchView B{b->n, 0, b->key_bytes, b->key_off, b->hits, b->limit, b->duration, b->burst, b->created_at,
-                    b->algorithm, b->behavior, b->is_owner, b->greg_expire, b->greg_duration, b->now_ms};
-        ResultView R{r->status, r->limit, r->remaining, r->reset_time, r->err};
-        r->over_limit_count = r->cache_hits = r->cache_misses = r->unexpired_evictions = 0; r->cache_size = 0;
-        const int rc = launch_batch(e, B, R);
+        clear_aggregates(results[k]);
+        const int rc = launch_batch(e, view_of(batches[k]), view_of(results[k]));
         if (rc) return rc;
         if (done) *done = k + 1;
     }

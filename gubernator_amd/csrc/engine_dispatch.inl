@@ -1,5 +1,6 @@
 // engine_dispatch.inl — part of guber_engine.hip's translation unit (included there, in this order; not a header of its own):
-// one dispatcher for several engines: fused launches of up to four tables, the held-back k_eval3 (GUBER_FUSE_EP), guber_eval_batches_routed_dev.
+// one dispatcher for several engines: EngineLocks (several engines' mutexes at once), fused launches of up to four tables, the held-back
+// k_eval3 (GUBER_FUSE_EP), guber_eval_batches_routed_dev.  The two-launch pipeline's groups are planned and launched by PairGroup (engine_batch.inl).
 // One dispatcher for several engines (the logical shards of a GPU, each a table of its own): batch k goes to
 // engines[which[k]]; per engine the array order is kept, between engines there is nothing to order (disjoint keys, no
 // shared state).  Each round takes the next batch of every engine that has one and, where the engines share device and
@@ -56,13 +57,28 @@ static void ep_flush_held(const guber_engine* e) {
     (void)launch_held(*e->held, false);
     e->held = nullptr;
 }
+// Several engines' mutexes at once: taken in ADDRESS order — the rule of every path that holds more than one (fused launches,
+// guber_stages_submit, a routed stage, guber_move_items_by_hash, the GLOBAL tick), so that any two of them agree — and given back in reverse.
+struct EngineLocks {
+    static constexpr int kMax = 64;                                // (a group of tables: <= MULTI_MEM_MAX; the GLOBAL tick's local ranks: <= GS_MAX_WORLD)
+    guber_engine* o[kMax]; int n;
+    template <typename EngineOf> EngineLocks(int count, EngineOf engine_of) : n(count) {
+        for (int i = 0; i < n; ++i) o[i] = engine_of(i);
+        std::sort(o, o + n);
+        for (int i = 0; i < n; ++i) o[i]->mu.lock();
+    }
+    EngineLocks(const EngineLocks&) = delete;
+    EngineLocks& operator=(const EngineLocks&) = delete;
+    void release() { while (n) o[--n]->mu.unlock(); }
+    ~EngineLocks() { release(); }
+    // a k_eval3 ANOTHER call holds back for one of these tables goes first (keep: the caller's own, which its next launch may take along)
+    void launch_held_by_others(const PendingEval* keep = nullptr) {
+        for (int i = 0; i < n; ++i) if (o[i]->held && o[i]->held != keep) { (void)launch_held(*o[i]->held, false); o[i]->held = nullptr; }
+    }
+};
 // the dispatcher's own: with all of its engines locked (engines_locked) or locking them here
 static int flush_pending(PendingEval& p, bool engines_locked = false) {
-    guber_engine* order[MULTI_MAX];
-    for (int i = 0; i < p.n; ++i) order[i] = p.eng[i];
-    std::sort(order, order + p.n);
-    if (!engines_locked) for (int i = 0; i < p.n; ++i) order[i]->mu.lock();
-    struct Unlock { guber_engine** o; int g; ~Unlock() { for (int i = g - 1; i >= 0; --i) o[i]->mu.unlock(); } } unlock{order, engines_locked ? 0 : p.n};
+    EngineLocks locks(engines_locked ? 0 : p.n, [&](int i) { return p.eng[i]; });
     const int rc = launch_held(p, true);
     for (int i = 0; i < p.n; ++i) if (p.eng[i]->held == &p) p.eng[i]->held = nullptr;
     return rc;
@@ -107,17 +123,15 @@ struct DpSpan { int k; uint64_t t0; explicit DpSpan(int kk) : k(kk), t0(dp_now()
 struct GroupItem { BatchView B; ResultView R; };
 static int launch_group(guber_engine* const* grp, const GroupItem* it, int g, uint32_t* enqueued, PendSet* ps = nullptr, EvalHook* hook = nullptr) {
     if (g_dprof) { tl_dp[5]++; tl_dp[6] += (uint64_t)g; }
-    auto views = [&](int i, BatchView& B, ResultView& R) { B = it[i].B; R = it[i].R; };
     // (one batch: launch_batch.  Measured in round 5 and not kept: a sequence of ONE table's batches through these fused launches —
     // 1.50 against 2.40 G decisions/s: 128 k_own workgroups for the whole chip take 36 us, profiles/r05_g_one_table_fused.txt)
     if (g == 1) {
         guber_engine* e = grp[0];
         if (ps) { const int rc = ps->flush_touching(grp, 1); if (rc) return rc; }
-        std::lock_guard<std::mutex> lk(e->mu);
-        if (e->held) { (void)launch_held(*e->held, false); e->held = nullptr; }      // (another call's)
+        EngineLocks locks(1, [&](int) { return e; });
+        locks.launch_held_by_others();
         if (e->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
-        BatchView B; ResultView R; views(0, B, R);
-        const int rc = launch_batch(e, B, R);
+        const int rc = launch_batch(e, it[0].B, it[0].R);
         if (rc == 0) ++*enqueued;
         return rc;
     }
@@ -139,15 +153,10 @@ static int launch_group(guber_engine* const* grp, const GroupItem* it, int g, ui
         if (rc0) return rc0;
     }
     // lock the group's engines in address order (any other caller holds at most one engine lock, or locks in this order)
-    guber_engine* order[MULTI_MAX];
     uint64_t dp_t = dp_now();
     auto dp_lap = [&](int k) { if (g_dprof) { const uint64_t t = dp_now(); tl_dp[k] += t - dp_t; dp_t = t; } };
-    for (int i = 0; i < g; ++i) order[i] = grp[i];
-    std::sort(order, order + g);
-    for (int i = 0; i < g; ++i) order[i]->mu.lock();
-    struct Unlock { guber_engine** o; int g; ~Unlock() { for (int i = g - 1; i >= 0; --i) o[i]->mu.unlock(); } } unlock{order, g};
-    for (int i = 0; i < g; ++i)                                    // a k_eval3 ANOTHER call holds back for one of these tables goes first
-        if (grp[i]->held && grp[i]->held != pend) { (void)launch_held(*grp[i]->held, false); grp[i]->held = nullptr; }
+    EngineLocks locks(g, [&](int i) { return grp[i]; });
+    locks.launch_held_by_others(pend);
     if (grp[0]->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
     {   // can_fuse() looked at the cache bound BEFORE these locks were taken (it takes and drops each engine's mutex): another thread's
         // AddCacheItem / eval on one of the tables may have used the headroom since.  Looked at again here, under the locks, with the
@@ -157,16 +166,14 @@ static int launch_group(guber_engine* const* grp, const GroupItem* it, int g, ui
         for (int i = 0; i < g; ++i) tight = tight || grp[i]->size_upper + it[i].B.n > grp[i]->cache_size;
         if (tight) {
             if (pend && pend->valid) { const int rcf = flush_pending(*pend, true); if (rcf) return rcf; }
-            for (int i = g - 1; i >= 0; --i) order[i]->mu.unlock();
-            unlock.g = 0;
+            locks.release();
             int rc1 = 0;
             for (int i = 0; i < g && !rc1; ++i) rc1 = launch_group(&grp[i], &it[i], 1, enqueued, ps, hook);
             return rc1;
         }
     }
     MultiFront MF{}; MultiEval ME{};
-    uint32_t tiles = 0, ns[MULTI_MAX];
-    int planned = 0, rc = 0;
+    int rc = 0;
     bool part = true;                                              // the group takes the owner-partitioned pipeline if all its batches do
     for (int i = 0; i < g; ++i) part = part && takes_part_path(grp[i], it[i].B.n, false, true);
     // GUBER_FUSE_EP: the k_eval3 held back on this stream shares this group's first launch if the group is the same tables again, in
@@ -175,9 +182,20 @@ static int launch_group(guber_engine* const* grp, const GroupItem* it, int g, ui
     bool join = ep && pend && pend->valid;
     if (pend && pend->valid && !join) { rc = flush_pending(*pend, true); if (rc) return rc; }   // (pend => the same engines: locked)
     dp_lap(1);
+    if (!part) {                                                  // the two-launch pipeline (join is false here: plain preludes, in the group's order)
+        PairGroup pg(MF, ME);
+        for (int i = 0; i < g && !rc; ++i) rc = pg.add(grp[i], it[i].B, it[i].R, false);   // (after an error: enqueue what is planned, then report)
+        dp_lap(2);
+        const int rcl = pg.launch(PairGroup::MULTI, true);        // (k_front_multi also for a group that an error cut to one table)
+        *enqueued += (uint32_t)pg.planned;
+        return rcl ? rcl : rc;
+    }
+    uint32_t tiles = 0;
+    uint64_t units = 0;
+    int planned = 0;
     for (int i = 0; i < g; ++i) {
         guber_engine* e = grp[i];
-        BatchView B; ResultView R; views(i, B, R);
+        const BatchView& B = it[i].B; const ResultView& R = it[i].R;
         Work W; FastPlan P;
         bool defer = false;
         rc = batch_prelude(e, B, W, join ? &defer : nullptr);
@@ -186,94 +204,78 @@ static int launch_group(guber_engine* const* grp, const GroupItem* it, int g, ui
             rc = flush_pending(*pend, true);
             if (!rc) rc = batch_prelude(e, B, W);
         }
-        if (!rc) rc = part ? plan_part(e, B, W, P) : plan_fast(e, B, false, W, P);
+        if (!rc) rc = plan_part(e, B, W, P);
         if (rc) break;                                            // enqueue what is planned, then report
-        tiles += P.ftiles;
+        tiles += P.ftiles; units += B.n;
         MF.end_tile[planned] = ME.end_tile[planned] = tiles;
         MF.sub[planned] = FrontArgs{e->T, P.B2, P.W};
         ME.sub[planned] = EvalArgs{e->T, P.B3, R, P.W};
-        ns[planned++] = B.n;
+        ++planned;
     }
     dp_lap(2);
-    if (planned) {
-        static_assert(FT == 256, "k_eval2's workgroup is k_front's tile");
-        MF.nb = ME.nb = (uint32_t)planned;
-        uint64_t units = 0;
-        for (int i = 0; i < planned; ++i) units += ns[i];
-        if (part) {
-            // (a prelude that was not quiet after all — a counter read-back now rides on this k_part — or a group cut short by an
-            // error: the k_eval3 held back goes first)
-            bool joined = join && pend->valid && planned == g;
-            for (int i = 0; i < planned && joined; ++i) joined = MF.sub[i].T.buckets == pend->ME.sub[i].T.buckets;
-            if (pend && pend->valid && !joined) { const int rcf = flush_pending(*pend, true); if (rcf) return rcf; }
-            // a counter read-back riding on this k_part runs beside the held-back k_eval3: what it reads lies between the counters
-            // before and after that batch, so the host counts that batch's requests among "enqueued since" as well (rb_fold_slot)
-            for (int i = 0; i < planned && joined; ++i) {
-                if (!MF.sub[i].W.snap_seq) continue;
-                for (auto& slot : grp[i]->rb)
-                    if (slot.armed && slot.seq == MF.sub[i].W.snap_seq) slot.mark -= std::min<uint64_t>(slot.mark, pend->ME.sub[i].B.n);
-            }
-            if (joined) {
-                // ONE launch: workgroups [0, pending tiles) are the held-back k_eval3, the rest this group's k_part
-                MultiEP EP{};
-                EP.nb = (uint32_t)planned;
-                for (int i = 0; i < planned; ++i) {
-                    EP.end_e[i] = pend->ME.end_tile[i]; EP.end_p[i] = MF.end_tile[i];
-                    EP.sub[i].E = pend->ME.sub[i]; EP.sub[i].Bp = MF.sub[i].B; EP.sub[i].did_p = MF.sub[i].W.did; EP.sub[i].pmslot_p = MF.sub[i].W.pmslot;
-                    const Work& Wp = MF.sub[i].W;
-                    EP.sub[i].snap_seq = Wp.snap_seq; EP.sub[i].snap_n = Wp.snap_n; EP.sub[i].snap_c = Wp.snap_c; EP.sub[i].snap_b = Wp.snap_b; EP.sub[i].snap_stamp = Wp.snap_stamp;
-                }
-                EvalHook* joined_hook;
-                { std::lock_guard<std::mutex> pl(pend->pm); pend->valid = false; joined_hook = pend->hook; pend->hook = nullptr; }
-                for (int i = 0; i < planned; ++i) grp[i]->held = nullptr;
-                dp_lap(3);
-                grp[0]->span_begin(KT_EVALPART_MULTI, pend->units);
-                hipLaunchKernelGGL(k_evalpart_multi, dim3(pend->tiles + tiles), dim3(256), 0, grp[0]->stream, EP);
-                grp[0]->span_end();
-                if (joined_hook) joined_hook->launched();
-                grp[0]->ep_launches++;
-            } else {
-                dp_lap(3);
-                grp[0]->span_begin(KT_PART_MULTI, units);
-                hipLaunchKernelGGL(k_part_multi, dim3(tiles), dim3(FT), 0, grp[0]->stream, MF);
-                grp[0]->span_end();
-            }
-            grp[0]->span_begin(KT_OWN_MULTI, units);
-            hipLaunchKernelGGL(k_own_multi, dim3((unsigned)planned * PT_PARTS), dim3(256), 0, grp[0]->stream, MF);
-            grp[0]->span_end();
-            dp_lap(4);
-            if (ep && planned == g) {                             // held back: the same tables' next group, or flush_pending, launches it
-                if (!pend) pend = ps->slot_for(grp, planned);
-                {
-                    std::lock_guard<std::mutex> pl(pend->pm);
-                    pend->valid = true; pend->n = planned; pend->tiles = tiles; pend->units = units; pend->ME = ME;
-                    pend->hook = hook;
-                    if (hook) hook->outstanding.fetch_add(1);
-                }
-                for (int i = 0; i < planned; ++i) { pend->eng[i] = grp[i]; grp[i]->held = pend; grp[i]->batches++; grp[i]->part_batches++; grp[i]->fused_batches++; }
-                *enqueued += (uint32_t)planned;
-                if (hipGetLastError() != hipSuccess) return fail(GUBER_E_HIP, "kernel launch");
-                dp_lap(3);
-                return rc;
-            }
-            grp[0]->span_begin(KT_EVAL3_MULTI, units);
-            hipLaunchKernelGGL(k_eval3_multi, dim3(tiles), dim3(256), 0, grp[0]->stream, ME);
-            grp[0]->span_end();
-            for (int i = 0; i < planned; ++i) { grp[i]->batches++; grp[i]->part_batches++; grp[i]->fused_batches++; }
-            *enqueued += (uint32_t)planned;
-            if (hipGetLastError() != hipSuccess) return fail(GUBER_E_HIP, "kernel launch");
-            return rc;
+    if (!planned) return rc;
+    MF.nb = ME.nb = (uint32_t)planned;
+    // (a prelude that was not quiet after all — a counter read-back now rides on this k_part — or a group cut short by an
+    // error: the k_eval3 held back goes first)
+    bool joined = join && pend->valid && planned == g;
+    for (int i = 0; i < planned && joined; ++i) joined = MF.sub[i].T.buckets == pend->ME.sub[i].T.buckets;
+    if (pend && pend->valid && !joined) { const int rcf = flush_pending(*pend, true); if (rcf) return rcf; }
+    // a counter read-back riding on this k_part runs beside the held-back k_eval3: what it reads lies between the counters
+    // before and after that batch, so the host counts that batch's requests among "enqueued since" as well (rb_fold_slot)
+    for (int i = 0; i < planned && joined; ++i) {
+        if (!MF.sub[i].W.snap_seq) continue;
+        for (auto& slot : grp[i]->rb)
+            if (slot.armed && slot.seq == MF.sub[i].W.snap_seq) slot.mark -= std::min<uint64_t>(slot.mark, pend->ME.sub[i].B.n);
+    }
+    if (joined) {
+        // ONE launch: workgroups [0, pending tiles) are the held-back k_eval3, the rest this group's k_part
+        MultiEP EP{};
+        EP.nb = (uint32_t)planned;
+        for (int i = 0; i < planned; ++i) {
+            EP.end_e[i] = pend->ME.end_tile[i]; EP.end_p[i] = MF.end_tile[i];
+            EP.sub[i].E = pend->ME.sub[i]; EP.sub[i].Bp = MF.sub[i].B; EP.sub[i].did_p = MF.sub[i].W.did; EP.sub[i].pmslot_p = MF.sub[i].W.pmslot;
+            const Work& Wp = MF.sub[i].W;
+            EP.sub[i].snap_seq = Wp.snap_seq; EP.sub[i].snap_n = Wp.snap_n; EP.sub[i].snap_c = Wp.snap_c; EP.sub[i].snap_b = Wp.snap_b; EP.sub[i].snap_stamp = Wp.snap_stamp;
         }
-        grp[0]->span_begin(KT_FRONT_MULTI, units);                    // (per-kernel timing, when enabled, is kept by the group's first engine)
-        hipLaunchKernelGGL(k_front_multi, dim3(tiles), dim3(FT), 0, grp[0]->stream, MF);
+        EvalHook* joined_hook;
+        { std::lock_guard<std::mutex> pl(pend->pm); pend->valid = false; joined_hook = pend->hook; pend->hook = nullptr; }
+        for (int i = 0; i < planned; ++i) grp[i]->held = nullptr;
+        dp_lap(3);
+        grp[0]->span_begin(KT_EVALPART_MULTI, pend->units);
+        hipLaunchKernelGGL(k_evalpart_multi, dim3(pend->tiles + tiles), dim3(256), 0, grp[0]->stream, EP);
         grp[0]->span_end();
-        grp[0]->span_begin(KT_EVAL2_MULTI, units);
-        hipLaunchKernelGGL(k_eval2_multi, dim3(tiles), dim3(256), 0, grp[0]->stream, ME);
+        if (joined_hook) joined_hook->launched();
+        grp[0]->ep_launches++;
+    } else {
+        dp_lap(3);
+        grp[0]->span_begin(KT_PART_MULTI, units);
+        hipLaunchKernelGGL(k_part_multi, dim3(tiles), dim3(FT), 0, grp[0]->stream, MF);
         grp[0]->span_end();
-        for (int i = 0; i < planned; ++i) { finish_fast(grp[i], ns[i]); grp[i]->fused_batches++; }
+    }
+    grp[0]->span_begin(KT_OWN_MULTI, units);
+    hipLaunchKernelGGL(k_own_multi, dim3((unsigned)planned * PT_PARTS), dim3(256), 0, grp[0]->stream, MF);
+    grp[0]->span_end();
+    dp_lap(4);
+    if (ep && planned == g) {                             // held back: the same tables' next group, or flush_pending, launches it
+        if (!pend) pend = ps->slot_for(grp, planned);
+        {
+            std::lock_guard<std::mutex> pl(pend->pm);
+            pend->valid = true; pend->n = planned; pend->tiles = tiles; pend->units = units; pend->ME = ME;
+            pend->hook = hook;
+            if (hook) hook->outstanding.fetch_add(1);
+        }
+        for (int i = 0; i < planned; ++i) { pend->eng[i] = grp[i]; grp[i]->held = pend; grp[i]->batches++; grp[i]->part_batches++; grp[i]->fused_batches++; }
         *enqueued += (uint32_t)planned;
         if (hipGetLastError() != hipSuccess) return fail(GUBER_E_HIP, "kernel launch");
+        dp_lap(3);
+        return rc;
     }
+    grp[0]->span_begin(KT_EVAL3_MULTI, units);
+    hipLaunchKernelGGL(k_eval3_multi, dim3(tiles), dim3(256), 0, grp[0]->stream, ME);
+    grp[0]->span_end();
+    for (int i = 0; i < planned; ++i) { grp[i]->batches++; grp[i]->part_batches++; grp[i]->fused_batches++; }
+    *enqueued += (uint32_t)planned;
+    if (hipGetLastError() != hipSuccess) return fail(GUBER_E_HIP, "kernel launch");
     return rc;
 }
 
@@ -284,45 +286,19 @@ static int launch_group(guber_engine* const* grp, const GroupItem* it, int g, ui
 // tables by its own call.  HA: device-visible host memory that stays untouched until the copy has run; DA: its place in HBM.
 // Returns 1 when a table turned out tight under the locks (nothing was enqueued: the caller takes the ordinary way), 0 / < 0 otherwise.
 static int launch_group_mem(guber_engine* const* grp, const GroupItem* it, int g, uint32_t* enqueued, MultiArgsMem* HA, MultiArgsMem* DA) {
-    guber_engine* order[MULTI_MEM_MAX];
-    for (int i = 0; i < g; ++i) order[i] = grp[i];
-    std::sort(order, order + g);
-    for (int i = 0; i < g; ++i) order[i]->mu.lock();
-    struct Unlock { guber_engine** o; int g; ~Unlock() { for (int i = g - 1; i >= 0; --i) o[i]->mu.unlock(); } } unlock{order, g};
-    for (int i = 0; i < g; ++i)                                    // a k_eval3 ANOTHER call holds back for one of these tables goes first
-        if (grp[i]->held) { (void)launch_held(*grp[i]->held, false); grp[i]->held = nullptr; }
+    EngineLocks locks(g, [&](int i) { return grp[i]; });
+    locks.launch_held_by_others();
     if (grp[0]->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
     for (int i = 0; i < g; ++i)
         if (grp[i]->size_upper + it[i].B.n > grp[i]->cache_size || grp[i]->small_pending) return 1;
-    uint32_t tiles = 0, ns[MULTI_MEM_MAX];
-    int planned = 0, rc = 0;
-    for (int i = 0; i < g; ++i) {
-        guber_engine* e = grp[i];
-        Work W; FastPlan P;
-        rc = batch_prelude(e, it[i].B, W);
-        if (!rc) rc = plan_fast(e, it[i].B, false, W, P);
-        if (rc) break;                                            // enqueue what is planned, then report
-        tiles += P.ftiles;
-        HA->F.end_tile[planned] = HA->E.end_tile[planned] = tiles;
-        HA->F.sub[planned] = FrontArgs{e->T, P.B2, P.W};
-        HA->E.sub[planned] = EvalArgs{e->T, P.B3, it[i].R, P.W};
-        ns[planned++] = it[i].B.n;
-    }
-    if (planned) {
-        HA->F.nb = HA->E.nb = (uint32_t)planned;
-        uint64_t units = 0;
-        for (int i = 0; i < planned; ++i) units += ns[i];
-        hipStream_t st = grp[0]->stream;
-        if (hipMemcpyAsync(DA, HA, sizeof(MultiArgsMem), hipMemcpyHostToDevice, st) != hipSuccess) return fail(GUBER_E_HIP, "hipMemcpyAsync");
-        grp[0]->span_begin(KT_FRONT_MULTI, units);
-        hipLaunchKernelGGL(k_front_multi_mem, dim3(tiles), dim3(FT), 0, st, (const MultiFrontMem*)&DA->F);
-        grp[0]->span_end();
-        grp[0]->span_begin(KT_EVAL2_MULTI, units);
-        hipLaunchKernelGGL(k_eval2_multi_mem, dim3(tiles), dim3(256), 0, st, (const MultiEvalMem*)&DA->E);
-        grp[0]->span_end();
-        for (int i = 0; i < planned; ++i) { finish_fast(grp[i], ns[i]); grp[i]->fused_batches++; }
-        *enqueued += (uint32_t)planned;
-        if (hipGetLastError() != hipSuccess) return fail(GUBER_E_HIP, "kernel launch");
+    PairGroup pg(HA, DA);
+    int rc = 0;
+    for (int i = 0; i < g && !rc; ++i) rc = pg.add(grp[i], it[i].B, it[i].R, false);   // (after an error: enqueue what is planned, then report)
+    if (pg.planned) {
+        if (hipMemcpyAsync(DA, HA, sizeof(MultiArgsMem), hipMemcpyHostToDevice, grp[0]->stream) != hipSuccess) return fail(GUBER_E_HIP, "hipMemcpyAsync");
+        const int rcl = pg.launch(PairGroup::MULTI_MEM, true);
+        *enqueued += (uint32_t)pg.planned;
+        if (rcl) return rcl;
     }
     return rc;
 }
@@ -371,12 +347,9 @@ extern "C" int guber_eval_batches_routed_dev(guber_engine_t* const* engines, uin
         if (which[k] >= n_engines || !engines[which[k]]) return fail(GUBER_E_INVALID_ARG, "which[k] names no engine");
         const int rc = check_batch_args(&batches[k], &results[k]);
         if (rc) return rc;
-        const guber_batch_t* b = &batches[k]; guber_result_t* r = &results[k];
-        r->over_limit_count = r->cache_hits = r->cache_misses = r->unexpired_evictions = 0; r->cache_size = 0;
-        if (!b->n) { ++empty; continue; }
-        fifo[which[k]].push_back(GroupItem{BatchView{b->n, 0, b->key_bytes, b->key_off, b->hits, b->limit, b->duration, b->burst, b->created_at,
-                                                     b->algorithm, b->behavior, b->is_owner, b->greg_expire, b->greg_duration, b->now_ms},
-                                           ResultView{r->status, r->limit, r->remaining, r->reset_time, r->err}});
+        clear_aggregates(results[k]);
+        if (!batches[k].n) { ++empty; continue; }
+        fifo[which[k]].push_back(GroupItem{view_of(batches[k]), view_of(results[k])});
     }
     uint32_t enqueued = 0;
     // GUBER_FUSE_EP engines: the k_eval3 of a group of tables is held back for the same tables' next group (launch_group)

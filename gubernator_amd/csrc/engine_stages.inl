@@ -1,5 +1,7 @@
 // engine_stages.inl — part of guber_engine.hip's translation unit (included there, in this order; not a header of its own):
-// stages: the overlapped end-to-end path, groups of stages in one submission, the stage routed to several engines.
+// stages: the overlapped end-to-end path, groups of stages in one submission, the stage routed to several engines.  Groups take the
+// two-launch pipeline through PairGroup (engine_batch.inl) and their engines' mutexes through EngineLocks (engine_dispatch.inl); what is
+// this file's own is how the argument blocks and the request columns reach HBM, and the stages' completion events.
 // ---- stages: batch buffers in device-visible host memory that the CALLER fills in place and the kernels read / write in
 // place.  A batcher that owns two of them fills one while the GPU evaluates the other: no staging copy, no copy launch,
 // no allocation per batch (what SURVEY.md section 8d calls the overlapped end-to-end path).
@@ -132,9 +134,8 @@ extern "C" int guber_stage_submit(guber_stage_t* s) {
     std::lock_guard<std::mutex> lk(e->mu);
     if (e->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
     if (e->small_pending) { const int rcp = resolve_small_locked(e->small_pending, true, e); if (rcp < 0) return rcp; }
-    BatchView B{b.n, 0, b.key_bytes, b.key_off, b.hits, b.limit, b.duration, b.burst, b.created_at, b.algorithm, b.behavior, b.is_owner,
-                b.greg_expire, b.greg_duration, b.now_ms};
-    ResultView R{s->result.status, s->result.limit, s->result.remaining, s->result.reset_time, s->result.err};
+    BatchView B = view_of(b);
+    const ResultView R = view_of(s->result);
     if (b.n <= FT && !e->no_small && !lru_may_bind(e, b.n)) {
         s->seq = ++e->small_seq ? e->small_seq : ++e->small_seq;
         s->sout->done = 0;
@@ -326,11 +327,7 @@ static int resolve_small_locked(guber_stage* s, bool block, guber_engine* holder
     }
     e->small_fallbacks++;
     if (e->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
-    const guber_batch_t& b = s->batch;
-    BatchView B{b.n, 0, b.key_bytes, b.key_off, b.hits, b.limit, b.duration, b.burst, b.created_at, b.algorithm, b.behavior, b.is_owner,
-                b.greg_expire, b.greg_duration, b.now_ms};
-    ResultView R{s->result.status, s->result.limit, s->result.remaining, s->result.reset_time, s->result.err};
-    int rc = launch_batch(e, B, R, true);
+    int rc = launch_batch(e, view_of(s->batch), view_of(s->result), true);
     if (rc) { s->mode = 0; return rc; }
     HIPCHK(hipEventRecord(s->ev, e->stream));
     s->gev = nullptr; s->mode = 2;
@@ -383,9 +380,8 @@ static int stage_views(guber_stage* s, StagePlan& P) {
     guber_engine* e = s->e;
     const guber_batch_t& b = s->batch;
     P.s = s;
-    P.B = BatchView{b.n, 0, b.key_bytes, b.key_off, b.hits, b.limit, b.duration, b.burst, b.created_at, b.algorithm, b.behavior, b.is_owner,
-                    b.greg_expire, b.greg_duration, b.now_ms};
-    P.R = ResultView{s->result.status, s->result.limit, s->result.remaining, s->result.reset_time, s->result.err};
+    P.B = view_of(b);
+    P.R = view_of(s->result);
     P.copy = e->stage_dma && b.n >= e->stage_copy_min && !b.greg_expire && !b.greg_duration;
     P.in = StageIn{};
     if (!P.copy) return 0;
@@ -417,73 +413,37 @@ static int launch_stage_group(StagePlan* P, int g) {
     guber_engine* e0 = P[0].s->e;
     const bool mem_args = g > MULTI_MAX;
     MultiStageIn MI{}; MultiFront MF{}; MultiEval ME{};
-    MultiArgsMem* HA = P[0].s->h_margs;
-    uint32_t tiles = 0; int planned = 0, rc = 0; bool any_copy = false;
-    FastPlan FP[MULTI_MEM_MAX];
-    for (int i = 0; i < g; ++i) {
-        guber_engine* e = P[i].s->e;
-        Work W;
-        rc = batch_prelude(e, P[i].B, W);
-        if (!rc) rc = plan_fast(e, P[i].B, !P[i].copy, W, FP[i]);
-        if (rc) break;
-        tiles += FP[i].ftiles;
-        if (mem_args) {
-            HA->F.end_tile[planned] = HA->E.end_tile[planned] = tiles;
-            HA->F.sub[planned] = FrontArgs{e->T, FP[i].B2, FP[i].W};
-            HA->E.sub[planned] = EvalArgs{e->T, FP[i].B3, P[i].R, FP[i].W};
-        } else {
-            MF.end_tile[planned] = ME.end_tile[planned] = tiles;
-            MF.sub[planned] = FrontArgs{e->T, FP[i].B2, FP[i].W};
-            ME.sub[planned] = EvalArgs{e->T, FP[i].B3, P[i].R, FP[i].W};
-        }
-        MI.sub[planned] = P[i].in;
-        any_copy = any_copy || P[i].copy;
-        ++planned;
-    }
-    if (!planned) return rc;
-    hipStream_t st = e0->stream;
-    MultiArgsMem* DA = nullptr;
-    MI.nb = (uint32_t)planned;
+    MultiArgsMem* HA = P[0].s->h_margs; MultiArgsMem* DA = nullptr;
     if (mem_args) {
         if (e0->d_margs.ensure(sizeof(MultiArgsMem))) return GUBER_E_NOMEM;
         DA = (MultiArgsMem*)e0->d_margs.p;
-        HA->F.nb = HA->E.nb = (uint32_t)planned;
+    }
+    PairGroup pg = mem_args ? PairGroup(HA, DA) : PairGroup(MF, ME);
+    int rc = 0; bool any_copy = false;
+    for (int i = 0; i < g; ++i) {
+        rc = pg.add(P[i].s->e, P[i].B, P[i].R, !P[i].copy);
+        if (rc) break;                                            // enqueue what is planned, then report
+        MI.sub[i] = P[i].in;
+        any_copy = any_copy || P[i].copy;
+    }
+    const int planned = pg.planned;
+    if (!planned) return rc;
+    hipStream_t st = e0->stream;
+    MI.nb = (uint32_t)planned;
+    if (mem_args) {
         StageIn& a = MI.sub[MI.nb++];                                // the argument blocks: one more segment list of the copy kernel
         a = StageIn{};
         a.src = (const uint4*)HA; a.dst = (uint4*)DA; a.nseg = 2;
-        a.off16[0] = 0; a.n16[0] = (uint32_t)((offsetof(MultiFrontMem, sub) + (size_t)planned * sizeof(FrontArgs) + 15) / 16);
-        a.off16[1] = (uint32_t)(offsetof(MultiArgsMem, E) / 16); a.n16[1] = (uint32_t)((offsetof(MultiEvalMem, sub) + (size_t)planned * sizeof(EvalArgs) + 15) / 16);
+        margs_segments(planned, a.off16, a.n16);
     }
     if (any_copy || mem_args) {
         MI.wg_per = 64;
         hipLaunchKernelGGL(k_stage_in_multi, dim3(MI.nb * MI.wg_per), dim3(256), 0, st, MI);
     }
-    uint64_t units = 0;
-    for (int i = 0; i < planned; ++i) units += P[i].B.n;
-    if (planned == 1) {
-        e0->span_begin(KT_FRONT, units);
-        hipLaunchKernelGGL(k_front, dim3(FP[0].ftiles), dim3(FT), 0, st, e0->T, FP[0].B2, FP[0].W);
-        e0->span_end();
-        e0->span_begin(KT_EVAL2, units);
-        hipLaunchKernelGGL(k_eval2, dim3(FP[0].ftiles), dim3(256), 0, st, EvalArgs{e0->T, FP[0].B3, P[0].R, FP[0].W});
-        e0->span_end();
-    } else if (mem_args) {
-        e0->span_begin(KT_FRONT_MULTI, units);
-        hipLaunchKernelGGL(k_front_multi_mem, dim3(tiles), dim3(FT), 0, st, (const MultiFrontMem*)&DA->F);
-        e0->span_end();
-        e0->span_begin(KT_EVAL2_MULTI, units);
-        hipLaunchKernelGGL(k_eval2_multi_mem, dim3(tiles), dim3(256), 0, st, (const MultiEvalMem*)&DA->E);
-        e0->span_end();
-    } else {
-        MF.nb = ME.nb = (uint32_t)planned;
-        e0->span_begin(KT_FRONT_MULTI, units);
-        hipLaunchKernelGGL(k_front_multi, dim3(tiles), dim3(FT), 0, st, MF);
-        e0->span_end();
-        e0->span_begin(KT_EVAL2_MULTI, units);
-        hipLaunchKernelGGL(k_eval2_multi, dim3(tiles), dim3(256), 0, st, ME);
-        e0->span_end();
+    {   // one stage: the plain pair; a group counts as fused
+        const int rcl = pg.launch(planned == 1 ? PairGroup::SINGLE : mem_args ? PairGroup::MULTI_MEM : PairGroup::MULTI, planned > 1);
+        if (rcl) return rcl;
     }
-    if (hipGetLastError() != hipSuccess) return fail(GUBER_E_HIP, "kernel launch");
     guber_engine::GroupEv* G = nullptr; uint32_t gseq = 0;
     if (planned > 1) {
         G = &e0->gev[e0->gev_next++ % guber_engine::kGroupEvs];
@@ -495,8 +455,6 @@ static int launch_stage_group(StagePlan* P, int g) {
     }
     for (int i = 0; i < planned; ++i) {
         guber_stage* s = P[i].s;
-        finish_fast(s->e, P[i].B.n);
-        if (planned > 1) s->e->fused_batches++;
         s->gev = G; s->gev_seq = gseq;
         if (!G && hipEventRecord(s->ev, st) != hipSuccess) return fail(GUBER_E_HIP, "hipEventRecord");
         s->mode = 2;
@@ -528,10 +486,8 @@ extern "C" int guber_stages_submit(guber_stage_t* const* stages, uint32_t n, uin
     const int group_max = MULTI_MEM_MAX;
     auto flush = [&]() -> int {
         if (!g) return 0;
-        guber_engine* order[MULTI_MEM_MAX];
-        for (int i = 0; i < g; ++i) order[i] = grp[i].s->e;
-        std::sort(order, order + g);                               // engine locks in address order (launch_group's rule)
-        for (int i = 0; i < g; ++i) { order[i]->mu.lock(); ep_flush_held(order[i]); }
+        EngineLocks locks(g, [&](int i) { return grp[i].s->e; });
+        locks.launch_held_by_others();
         int rc = 0;
         if (grp[0].s->e->set_device()) rc = fail(GUBER_E_HIP, "hipSetDevice");
         for (int i = 0; i < g && !rc; ++i) {
@@ -540,7 +496,6 @@ extern "C" int guber_stages_submit(guber_stage_t* const* stages, uint32_t n, uin
             if (!rc) rc = stage_views(grp[i].s, grp[i]);
         }
         if (!rc) rc = launch_stage_group(grp, g);
-        for (int i = g - 1; i >= 0; --i) order[i]->mu.unlock();
         if (!rc) enq += (uint32_t)g;
         g = 0;
         return rc;
@@ -549,10 +504,7 @@ extern "C" int guber_stages_submit(guber_stage_t* const* stages, uint32_t n, uin
     guber_stage* sgrp[SMALL_MULTI_MAX]; int sg = 0;
     auto flush_small = [&]() -> int {
         if (!sg) return 0;
-        guber_engine* order[SMALL_MULTI_MAX];
-        for (int i = 0; i < sg; ++i) order[i] = sgrp[i]->e;
-        std::sort(order, order + sg);
-        for (int i = 0; i < sg; ++i) order[i]->mu.lock();
+        EngineLocks locks(sg, [&](int i) { return sgrp[i]->e; });
         int rc = 0, planned = 0;
         MultiSmall MS{};
         guber_engine* e0 = sgrp[0]->e;
@@ -560,15 +512,12 @@ extern "C" int guber_stages_submit(guber_stage_t* const* stages, uint32_t n, uin
         for (int i = 0; i < sg && !rc; ++i) {
             guber_stage* s = sgrp[i]; guber_engine* e = s->e;
             if (e->small_pending) { const int r2 = resolve_small_locked(e->small_pending, true, e); if (r2 < 0) { rc = r2; break; } }
-            const guber_batch_t& b = s->batch;
-            BatchView B{b.n, 0, b.key_bytes, b.key_off, b.hits, b.limit, b.duration, b.burst, b.created_at, b.algorithm, b.behavior, b.is_owner,
-                        b.greg_expire, b.greg_duration, b.now_ms};
+            const BatchView B = view_of(s->batch);
             rc = small_prelude(e, B);
             if (rc) break;
             s->seq = ++e->small_seq ? e->small_seq : ++e->small_seq;
             s->sout->done = 0;
-            MS.sub[planned] = SmallArgs{e->T, B, ResultView{s->result.status, s->result.limit, s->result.remaining, s->result.reset_time, s->result.err},
-                                        s->sout, e->touch, s->seq};
+            MS.sub[planned] = SmallArgs{e->T, B, view_of(s->result), s->sout, e->touch, s->seq};
             ++planned;
         }
         if (planned) {
@@ -579,7 +528,6 @@ extern "C" int guber_stages_submit(guber_stage_t* const* stages, uint32_t n, uin
             for (int i = 0; i < planned; ++i) { sgrp[i]->mode = 3; sgrp[i]->e->small_pending = sgrp[i]; }
             enq += (uint32_t)planned;
         }
-        for (int i = sg - 1; i >= 0; --i) order[i]->mu.unlock();
         sg = 0;
         return rc;
     };
@@ -605,11 +553,8 @@ extern "C" int guber_stages_submit(guber_stage_t* const* stages, uint32_t n, uin
         std::lock_guard<std::mutex> lk(e->mu);
         if (e->set_device()) { rc = fail(GUBER_E_HIP, "hipSetDevice"); break; }
         if (e->small_pending) { const int r2 = resolve_small_locked(e->small_pending, true, e); if (r2 < 0) { rc = r2; break; } }
-        BatchView B{b.n, 0, b.key_bytes, b.key_off, b.hits, b.limit, b.duration, b.burst, b.created_at, b.algorithm, b.behavior, b.is_owner,
-                    b.greg_expire, b.greg_duration, b.now_ms};
-        ResultView R{s->result.status, s->result.limit, s->result.remaining, s->result.reset_time, s->result.err};
         // the radix pipeline (n > 65 536) or a test configuration
-        rc = launch_batch(e, B, R, true);
+        rc = launch_batch(e, view_of(b), view_of(s->result), true);
         if (rc) break;
         if (hipEventRecord(s->ev, e->stream) != hipSuccess) { rc = fail(GUBER_E_HIP, "hipEventRecord"); break; }
         s->gev = nullptr; s->mode = 2;
@@ -735,11 +680,8 @@ extern "C" int guber_stage_submit_routed(guber_stage_t* s, guber_engine_t* const
     if (total != b.n) return fail(GUBER_E_INVALID_ARG, "the shares do not add up to the batch");
     if (b.n == 0) { s->mode = 0; return GUBER_OK; }
     memset((uint8_t*)b.key_bytes + b.key_off[b.n], 0, 16);            // the kernels read keys as 8-byte words
-    guber_engine* order[MULTI_MEM_MAX];
-    for (uint32_t j = 0; j < n_engines; ++j) order[j] = engines[j];
-    std::sort(order, order + n_engines);                             // engine locks in address order (launch_group's rule)
-    for (uint32_t j = 0; j < n_engines; ++j) { order[j]->mu.lock(); ep_flush_held(order[j]); }
-    struct Unlock { guber_engine** o; uint32_t n; ~Unlock() { for (uint32_t j = n; j-- > 0;) o[j]->mu.unlock(); } } unlock{order, n_engines};
+    EngineLocks locks((int)n_engines, [&](int j) { return engines[j]; });
+    locks.launch_held_by_others();
     guber_engine* e0 = s->e;
     if (e0->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
     for (uint32_t j = 0; j < n_engines; ++j)
@@ -750,7 +692,8 @@ extern "C" int guber_stage_submit_routed(guber_stage_t* s, guber_engine_t* const
         if (small_ok) {
             MultiSmallRouted MS{};
             s->parts.clear();
-            BatchView BH{0, 0, b.key_bytes, b.key_off, b.hits, b.limit, b.duration, b.burst, b.created_at, b.algorithm, b.behavior, b.is_owner, nullptr, nullptr, b.now_ms};
+            BatchView BH = view_of(b);                              // (no calendar columns: checked above)
+            BH.n = 0;
             for (uint32_t j = 0; j < n_engines; ++j) {
                 if (!counts[j]) continue;
                 guber_engine* e = engines[j];
@@ -764,7 +707,7 @@ extern "C" int guber_stage_submit_routed(guber_stage_t* s, guber_engine_t* const
                 s->parts.push_back(guber_stage::RoutedPart{e, j, counts[j], seq, out, true, 0});
             }
             MS.nb = (uint32_t)s->parts.size(); MS.n_total = b.n; MS.dest = s->h_dest; MS.B = BH;
-            MS.R = ResultView{s->result.status, s->result.limit, s->result.remaining, s->result.reset_time, s->result.err};
+            MS.R = view_of(s->result);
             hipLaunchKernelGGL(k_small_routed, dim3(MS.nb), dim3(FT), 0, e0->stream, MS);
             if (hipGetLastError() != hipSuccess) { s->parts.clear(); return fail(GUBER_E_HIP, "kernel launch"); }
             for (auto& part : s->parts) part.e->small_pending = s;
@@ -797,13 +740,14 @@ extern "C" int guber_stage_submit_routed(guber_stage_t* s, guber_engine_t* const
     A.behavior = b.behavior; A.algorithm = b.algorithm; A.is_owner = b.is_owner;
     A.key_src = (const uint4*)b.key_bytes; A.key_dst = (uint4*)d_keys; A.key_n16 = (uint32_t)(((size_t)b.key_off[b.n] + 16 + 15) / 16);
     MultiArgsMem* HA = s->h_margs; MultiArgsMem* DA = (MultiArgsMem*)e0->d_margs.p;
-    uint32_t tiles = 0, base = 0; int planned = 0;
-    guber_engine* took[MULTI_MEM_MAX]; uint32_t took_n[MULTI_MEM_MAX];
+    PairGroup pg(HA, DA);
+    pg.timer = e0;                                                   // (the stage's own engine keeps the per-kernel timing, whichever share comes first)
+    uint32_t base = 0;
     // a share that may overflow its engine's cache needs the eviction pre-pass (launch_batch), which reads the share's keys: then the
     // shares are brought to HBM first and evaluated engine by engine
     bool exact = false;
     for (uint32_t j = 0; j < n_engines; ++j) exact = exact || (counts[j] && lru_may_bind(engines[j], counts[j]));
-    BatchView XB[MULTI_MEM_MAX]; ResultView XR[MULTI_MEM_MAX];
+    guber_engine* xe[MULTI_MEM_MAX]; BatchView XB[MULTI_MEM_MAX]; ResultView XR[MULTI_MEM_MAX]; int nx = 0;
     for (uint32_t j = 0; j < n_engines; ++j) {
         A.base[j] = base;
         const uint32_t nj = counts[j];
@@ -812,30 +756,19 @@ extern "C" int guber_stage_submit_routed(guber_stage_t* s, guber_engine_t* const
         BatchView B{nj, 0, d_keys, A.d_key_off + base, A.d_hits + base, A.d_limit + base, A.d_duration + base, A.d_burst + base, A.d_created_at + base,
                     A.d_algorithm + base, A.d_behavior + base, A.d_is_owner + base, nullptr, nullptr, b.now_ms, 0, A.d_key_len + base};
         ResultView R{o_status + base, o_limit + base, o_remaining + base, o_reset + base, o_err + base};
-        if (exact) { XB[planned] = B; XR[planned] = R; took[planned] = e; took_n[planned] = nj; ++planned; base += nj; continue; }
-        Work W; FastPlan FP;
-        int rc = batch_prelude(e, B, W);
-        if (!rc) rc = plan_fast(e, B, false, W, FP);
-        if (rc) return rc;                                           // (nothing has been launched; the stage stays idle)
-        tiles += FP.ftiles;
-        HA->F.end_tile[planned] = HA->E.end_tile[planned] = tiles;
-        HA->F.sub[planned] = FrontArgs{e->T, FP.B2, FP.W};
-        HA->E.sub[planned] = EvalArgs{e->T, FP.B3, R, FP.W};
-        took[planned] = e; took_n[planned] = nj;
-        ++planned;
+        if (exact) { xe[nx] = e; XB[nx] = B; XR[nx] = R; ++nx; }
+        else { const int rc = pg.add(e, B, R, false); if (rc) return rc; }   // (nothing has been launched; the stage stays idle)
         base += nj;
     }
-    HA->F.nb = HA->E.nb = (uint32_t)planned;
     A.arg_src = (const uint4*)HA; A.arg_dst = (uint4*)DA;
-    A.arg_off16[0] = 0; A.arg_n16[0] = (uint32_t)((offsetof(MultiFrontMem, sub) + (size_t)planned * sizeof(FrontArgs) + 15) / 16);
-    A.arg_off16[1] = (uint32_t)(offsetof(MultiArgsMem, E) / 16); A.arg_n16[1] = (uint32_t)((offsetof(MultiEvalMem, sub) + (size_t)planned * sizeof(EvalArgs) + 15) / 16);
+    margs_segments(pg.planned, A.arg_off16, A.arg_n16);
     A.nb_req = (uint32_t)((n + 255) / 256);
     A.nb_key = keys_there ? 0u : std::max<uint32_t>(1u, std::min<uint32_t>(256u, (A.key_n16 + 1023) / 1024));
     A.nb_arg = 4;
     hipStream_t st = e0->stream;
     hipLaunchKernelGGL(k_stage_in_routed, dim3(A.nb_req + A.nb_key + A.nb_arg), dim3(256), 0, st, A);
     if (exact) {
-        for (int i = 0; i < planned; ++i) { const int rc = launch_batch(took[i], XB[i], XR[i]); if (rc) return rc; }
+        for (int i = 0; i < nx; ++i) { const int rc = launch_batch(xe[i], XB[i], XR[i]); if (rc) return rc; }
         hipLaunchKernelGGL(k_stage_out_routed, dim3(A.nb_req), dim3(256), 0, st, O);
         if (hipGetLastError() != hipSuccess) return fail(GUBER_E_HIP, "kernel launch");
         if (hipEventRecord(s->ev, st) != hipSuccess) return fail(GUBER_E_HIP, "hipEventRecord");
@@ -843,15 +776,12 @@ extern "C" int guber_stage_submit_routed(guber_stage_t* s, guber_engine_t* const
         s->gev = nullptr; s->mode = 2;
         return GUBER_OK;
     }
-    e0->span_begin(KT_FRONT_MULTI, n);
-    hipLaunchKernelGGL(k_front_multi_mem, dim3(tiles), dim3(FT), 0, st, (const MultiFrontMem*)&DA->F);
-    e0->span_end();
-    e0->span_begin(KT_EVAL2_MULTI, n);
-    hipLaunchKernelGGL(k_eval2_multi_mem, dim3(tiles), dim3(256), 0, st, (const MultiEvalMem*)&DA->E);
-    e0->span_end();
+    {
+        const int rc = pg.launch(PairGroup::MULTI_MEM, pg.planned > 1);
+        if (rc) return rc;
+    }
     hipLaunchKernelGGL(k_stage_out_routed, dim3(A.nb_req), dim3(256), 0, st, O);
     if (hipGetLastError() != hipSuccess) return fail(GUBER_E_HIP, "kernel launch");
-    for (int i = 0; i < planned; ++i) { finish_fast(took[i], took_n[i]); if (planned > 1) took[i]->fused_batches++; }
     if (hipEventRecord(s->ev, st) != hipSuccess) return fail(GUBER_E_HIP, "hipEventRecord");
     s->routed.assign(engines, engines + n_engines);
     s->gev = nullptr; s->mode = 2;

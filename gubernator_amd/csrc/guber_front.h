@@ -283,8 +283,7 @@ static int front_eval(guber_front* f, const FrontGen* gens, guber_result_t* resu
         if (gens[k].b.n > f->cap) return fail(GUBER_E_BATCH_TOO_LARGE, "generation larger than the front was created for");
         if (gens[k].b.greg_expire || gens[k].b.greg_duration) return fail(GUBER_E_INVALID_ARG, "a front takes its calendar intervals from the device");
         if (gens[k].key_stride & 7u) return fail(GUBER_E_INVALID_ARG, "key rows are a multiple of 8 bytes apart");
-        guber_result_t* r = &results[k];
-        r->over_limit_count = r->cache_hits = r->cache_misses = r->unexpired_evictions = 0; r->cache_size = 0;
+        clear_aggregates(results[k]);
     }
     std::lock_guard<std::mutex> lk(f->mu);
     if (hipSetDevice(f->device) != hipSuccess) return fail(GUBER_E_HIP, "hipSetDevice");

@@ -553,11 +553,9 @@ extern "C" int guber_global_sync(guber_comm_t* c, int64_t now_ms, guber_global_s
     guber_global_sync_stats_t st{};
     // every local rank's engine, locked in ADDRESS order — the rule of every path that holds several engines at once (fused
     // launches, guber_stages_submit, guber_move_items_by_hash) — and held until the tick is over
-    std::vector<guber_engine*> held;
-    for (GsRank* r : c->ranks) held.push_back(r->e);
-    std::sort(held.begin(), held.end());
-    for (guber_engine* e : held) { e->mu.lock(); ep_flush_held(e); }
-    struct Unlock { std::vector<guber_engine*>& h; ~Unlock() { for (size_t i = h.size(); i-- > 0;) h[i]->mu.unlock(); } } unlock{held};
+    static_assert((int)GS_MAX_WORLD <= EngineLocks::kMax, "a tick holds every local rank's engine");
+    EngineLocks locks((int)c->ranks.size(), [&](int i) { return c->ranks[i]->e; });
+    locks.launch_held_by_others();
     const uint32_t W = c->world;
     int rc = 0;
     // ---- A: pending hits -> rows grouped by owner ----

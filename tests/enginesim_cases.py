@@ -12,6 +12,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 
 import gubernator_amd as ga
+import stage_groups_check
 import streams
 import support
 
@@ -438,6 +439,7 @@ CASES = {
     "routed_lru": lambda: routed_lru(os.environ.get("GUBER_FUSE_EP") == "1"),
     "single_default": lambda: single(0),
     "single_part": lambda: single(ga.FLAG_TEST_FORCE_PART),
+    "stage_groups": stage_groups_check.main,
 }
 
 if __name__ == "__main__":

@@ -77,6 +77,14 @@ def test_a_front_routes_generations_on_the_device_and_answers_in_arrival_order(e
     run_case(enginesim, case, **env)
 
 
+def test_groups_of_stages_take_one_pair_of_launches(enginesim):
+    """guber_stages_submit with aggregates off (tests/stage_groups_check.py): one stage, three and six of engines that share a stream, twice —
+    every answer the oracle's, and the profile says which form each group took: k_front / k_eval2 for one stage, k_front_multi /
+    k_eval2_multi for three (arguments by value) and for six (arguments through device memory), exactly one pair per group"""
+    out = run_case(enginesim, "stage_groups")
+    assert "launches {'k_front': 2, 'k_eval2': 2, 'k_front_multi': 4, 'k_eval2_multi': 4}" in out, out[-500:]
+
+
 def test_a_front_sends_global_requests_to_the_global_engine(enginesim):
     """guber_route_rule_t.global_engine: Behavior_GLOBAL requests go to the device's GLOBAL engine, the rest by the placement"""
     run_case(enginesim, "front_global")

@@ -414,6 +414,17 @@ def test_pool_global_engine_and_hot_key_migration():
     inst.close()
 
 
+def test_groups_of_stages_take_one_pair_of_launches():
+    """guber_stages_submit with aggregates off (tests/stage_groups_check.py, in a process of its own: it reads the engines' per-kernel
+    timing): groups of one, three and six stages of engines that share a stream, twice — every answer the oracle's, and exactly one
+    k_front / k_eval2 pair per group of one, one k_front_multi / k_eval2_multi pair per group of three (arguments by value) and of six
+    (arguments through device memory)"""
+    import subprocess, sys
+    p = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "stage_groups_check.py")], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and "STAGE GROUPS CHECK OK" in p.stdout, (p.stdout[-2000:], p.stderr[-2000:])
+    assert "launches {'k_front': 2, 'k_eval2': 2, 'k_front_multi': 4, 'k_eval2_multi': 4}" in p.stdout, p.stdout[-500:]
+
+
 def test_the_go_bindings_call_sequence_in_plain_c(tmp_path):
     """tests/hostsim/abi_c99.c — the cgo preamble and the calls go/gpu_worker_pool.go makes, compiled as C99 — against the real
     library on the GPU: create, GetRateLimits with owner flags, AddCacheItem (GLOBAL), GetCacheItem, Load, Store, GlobalSync, Close; then

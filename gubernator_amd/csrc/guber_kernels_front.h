@@ -98,7 +98,9 @@ __global__ __launch_bounds__(FR_TILE) void k_fr_count(FrIn A) {
     __syncthreads();
     // the lanes of the wave that go to the same engine: four ballots (one per bit of the engine's number) instead of one per engine;
     // a lane's rank among them follows the arrival order (stable), the group's first lane leaves the group's size
-    unsigned long long same = __ballot(true);
+    // (lanes behind the generation's end carry 0xff, whose four low bits are engine 15's: they are in nobody's group, or engine 15's
+    //  count in the generation's last wave would include them)
+    unsigned long long same = __ballot(e <= 15u);
 #pragma unroll
     for (uint32_t b = 0; b < 4; ++b) { const unsigned long long m = __ballot((e >> b) & 1u); same &= ((e >> b) & 1u) ? m : ~m; }
     if (e > 15u) same = 0ull;                                        // (lanes behind the generation's end)

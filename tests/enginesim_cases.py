@@ -201,6 +201,7 @@ def single(flags):
 def dev_gen(hb, full):
     """a generation for guber_front_eval_dev: every column a "device" array (full: burst / created_at / is_owner too)"""
     n = hb.n
+    # (16 bytes more than the promised 8 behind the last key; the tight buffer is tests/front_edges.py pack())
     cols = dict(key_bytes=np.ascontiguousarray(np.concatenate([hb.key_bytes, np.zeros(16, np.uint8)])), key_off=np.ascontiguousarray(hb.key_off.view(np.int32)),
                 hits=np.ascontiguousarray(hb.hits), limit=np.ascontiguousarray(hb.limit), duration=np.ascontiguousarray(hb.duration),
                 algorithm=np.ascontiguousarray(hb.algorithm), behavior=np.ascontiguousarray(hb.behavior.view(np.int32)),
@@ -425,7 +426,53 @@ def front_global():
     place.close()
 
 
+def front_edges_case(n_engines):
+    """tests/front_edges.py's scenarios (key widths 1 .. 64, sizes around the thread stride and the tile, one odd key, skew, GLOBAL) through
+    guber_front_eval_dev on n_engines engines of one stream; the key buffers end exactly 8 bytes behind their last key (front_edges.pack),
+    so a kernel that reads further than include/guber_gpu.h allows is AddressSanitizer's report"""
+    import time
+    import front_edges as fe
+    t0 = time.perf_counter()
+    rng = np.random.default_rng(1600 + n_engines)
+    place = ga.Placement(n_engines)
+    place.observe_keys(*fe.observed_traffic(np.random.default_rng(77), n_engines))     # (the hot keys of the 15-byte population get places of their own)
+    place.rebalance(0.125, True)
+    assert place.n_hot() > 0
+    e0 = ga.Engine(cache_size=1 << 14, max_batch=4096)
+    engs = [e0] + [ga.Engine(cache_size=1 << 14, max_batch=4096, stream=e0.stream_handle()) for _ in range(n_engines - 1)]
+    scratch = ga.Engine(cache_size=64, max_batch=256)
+    errors = fe.error_answers(scratch)
+    scratch.close()
+    fr = ga.Front(engs, place, max_n=2049, depth=3, global_engine=n_engines - 1)
+    orc = support.Oracle(cache_size=1 << 20)
+
+    def device_side(hb, full, r):
+        cols = dict(key_bytes=hb.key_bytes, key_off=hb.key_off.view(np.int32), hits=hb.hits, limit=hb.limit, duration=hb.duration, algorithm=hb.algorithm,
+                    behavior=hb.behavior.view(np.int32), burst=hb.burst if full else None, created_at=hb.created_at if full else None,
+                    is_owner=hb.is_owner if full else None)
+        assert all(v is None or v.flags.c_contiguous for v in cols.values())
+        p = {k: (v.ctypes.data if v is not None else None) for k, v in cols.items()}
+        b = ga.GuberBatch(hb.n, 0, p["key_bytes"], p["key_off"], p["hits"], p["limit"], p["duration"], p["burst"], p["created_at"], p["algorithm"], p["behavior"],
+                          p["is_owner"], None, None, hb.now_ms)
+        res = ga.GuberResult(r["status"].ctypes.data, r["limit"].ctypes.data, r["remaining"].ctypes.data, r["reset_time"].ctypes.data, r["err"].ctypes.data, 0, 0, 0, 0, 0)
+        return b, res, (cols, r)
+
+    count, sizes = fe.drive(ga, engs, fr, place, orc, fe.generations(n_engines, place, rng, depth=3), device_side, lambda keep: keep[1], errors, n_engines - 1)
+    assert min(sizes) > 0, sizes
+    print(f"front_edges: {n_engines} engines, {count} generations, sizes {sizes}, {time.perf_counter() - t0:.1f} s")
+    fr.close()
+    for e in engs:
+        e.close()
+    place.close()
+
+
+def front_edges():
+    front_edges_case(16)
+    front_edges_case(3)
+
+
 CASES = {
+    "front_edges": front_edges,
     "front_global": front_global,
     "front_lru3": lambda: front_lru(3),
     "bench_sequence": bench_sequence,

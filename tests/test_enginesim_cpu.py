@@ -77,6 +77,14 @@ def test_a_front_routes_generations_on_the_device_and_answers_in_arrival_order(e
     run_case(enginesim, case, **env)
 
 
+def test_a_front_at_key_width_tile_and_sixteen_engine_edges(enginesim):
+    """tests/front_edges.py's scenarios a - d (packed key widths 1 .. 32 and single widths above, sizes around the thread stride and the
+    tile, one odd / empty / over-long key in a generation of one width, skew, GLOBAL) on fronts of 16 and of 3 engines: answers, the
+    engine every key is resident in, the host's hash against a plain-Python XXH64, sentinels behind the results.  The key buffers end
+    exactly the 8 bytes behind their last key that include/guber_gpu.h promises: a kernel that reads further is AddressSanitizer's report"""
+    run_case(enginesim, "front_edges")
+
+
 def test_groups_of_stages_take_one_pair_of_launches(enginesim):
     """guber_stages_submit with aggregates off (tests/stage_groups_check.py): one stage, three and six of engines that share a stream, twice —
     every answer the oracle's, and the profile says which form each group took: k_front / k_eval2 for one stage, k_front_multi /

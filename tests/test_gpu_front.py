@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 
 def dev_gen(torch, dev, hb, full):
     n = hb.n
+    # (16 bytes more than the promised 8 behind the last key; the tight buffer is tests/front_edges.py pack())
     cols = dict(key_bytes=np.concatenate([hb.key_bytes, np.zeros(16, np.uint8)]), key_off=hb.key_off.view(np.int32), hits=hb.hits, limit=hb.limit,
                 duration=hb.duration, algorithm=hb.algorithm, behavior=hb.behavior.view(np.int32),
                 burst=hb.burst if full else None, created_at=hb.created_at if full else None, is_owner=hb.is_owner if full else None)   # (None: the column is absent)

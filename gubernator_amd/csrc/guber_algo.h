@@ -552,6 +552,37 @@ GB_HD uint32_t eval_uniform_rank_1x(const Rec& s0, const Req& r, int64_t now, ui
     }
 }
 
+// The shortcuts of skip() as one step, for a caller that runs the loop of eval_uniform_rank_1x() itself (the evaluation core of
+// k_eval2 / k_eval3, guber_kernels.h eval_core): after ONE application of a run's request r (`before` -> `s`) with k > 0 further
+// applications due, what to do about those k — k = 0 at a fixed point; parity settled and k = 0 on a period-2 cycle (prev2 = the
+// state two steps ago, if have_prev2); an observed plain subtraction extrapolated; anything else leaves k alone and the caller
+// steps on.  (skip() and eval_uniform_rank_1x() keep these steps spelt out: calling this function from them computes the same
+// but moves the register allocation of the kernels that inline them, k_eval and k_small.)
+GB_HD void run_step(const Rec& before, Rec& s, Rec& prev2, bool& have_prev2, uint64_t& k, const Req& r, int64_t now) {
+    if (rec_eq(s, before)) { k = 0; return; }                           // fixed point
+    if (have_prev2 && rec_eq(s, prev2)) {                               // period 2
+        if (k & 1) s = before;
+        k = 0;
+        return;
+    }
+    prev2 = before; have_prev2 = true;
+    if (pure_subtract(before, s, r, now)) {
+        const uint32_t kind = rec_kind(s);
+        const int64_t n = kind == K_TOKEN ? s.remaining : go_f2i(bits2f(s.remaining));
+        if (n > 0) {
+            const uint64_t m = (uint64_t)(n - 1) / (uint64_t)r.hits;
+            const uint64_t j = m < k ? m : k;
+            if (j > 0) {
+                const int64_t dec = (int64_t)(j * (uint64_t)r.hits);    // <= n-1, exact
+                if (kind == K_TOKEN) s.remaining -= dec;
+                else s.remaining = f2bits(bits2f(s.remaining) - (double)dec);
+                k -= j;
+                have_prev2 = false;
+            }
+        }
+    }
+}
+
 // ---- closed forms for the regimes real traffic lives in ---------------------------------------
 // A run of identical requests with hits = h > 0 against a LIVE bucket whose configuration the request does not
 // change is a counter walk on the integer level I (token: Remaining; leaky: int64(Remaining)): while I > h the

@@ -477,6 +477,145 @@ __global__ __launch_bounds__(FT) void k_front(Table T, BatchView B, Work W) { fr
 
 struct EvalArgs { Table T; BatchView B; ResultView R; Work W; };
 
+// ---- what k_eval2 and k_eval3 (guber_kernels_part.h) share: everything from "the request knows its segment" on ------------------
+// The two kernels differ in how a request learns its segment (bucket before the batch, slot, rank, total, flags), in how `parallel` is
+// decided for a leaky run whose created_at differs, and in the iterator that yields a walked segment's requests.  The rest is here, once.
+
+// Is this a wave in which EVERY request is the common case — a live token bucket met by a request that does not reconfigure it, nothing
+// flagged (`special`: the kernel's own per-request exceptions), no Store side channel, no GLOBAL bookkeeping?  Such a wave runs straight
+// through the closed form (eval_plain): one ballot instead of the general path's cascade of divergent branches (error codes, flags, the
+// leaky form, the serial walk, events, queues), each of which costs every wave its exec-mask bookkeeping whether a lane takes it or not.
+__device__ __forceinline__ bool eval_plain_wave(const Table& T, const BatchView& B, const Work& W, const bool live, const bool special,
+                                                const uint32_t sf, const uint32_t smeta, const Rec& s0, const Req& r) {
+    const bool plain = !live || (!special && sf == 0u && !(smeta & SM_HAS_INVALID) && token_fast_ok(s0, r, B.now_ms));
+    return !W.store_flags && !T.gpend && __ballot(!plain) == 0ull;
+}
+// one request of such a wave: exactly eval_core's own steps for it (token_fast_ok -> token_fast -> store -> the run's last request
+// writes the bucket), so the results are the same by construction
+__device__ __forceinline__ void eval_plain(const Table& T, const ResultView& R, const Work& W, const uint32_t i, const Req& r, const Rec& s0, const uint32_t slot,
+                                           const uint32_t rank, const uint32_t total, int& c_over, int& c_hit, int& c_miss, int& c_size) {
+    Rec after; Resp out;
+    const uint32_t ev = token_fast(s0, r, rank, out, after);
+    store_resp(R, i, out);
+    c_over = (ev & EV_OVER) ? 1 : 0; c_hit = (ev & EV_HIT) ? 1 : 0; c_miss = (ev & EV_MISS) ? 1 : 0;
+    if (rank == total - 1) {
+        rec_set_stamp(after, W.touch + i);                    // the key's place in the recency order: its last request (lrucache.go:111-128)
+        T.buckets[slot].rec = after;
+        c_size = (int)(rec_kind(after) != K_ABSENT) - (int)(rec_kind(s0) != K_ABSENT);
+    }
+}
+
+// The evaluation of request i (r; its segment's bucket before the batch s0 at `slot`; the request is number `rank` of the segment's
+// `total`).  parallel: the segment is a run of requests that are identical as far as the bucket is concerned, every request evaluates its
+// own rank; otherwise the segment's first request walks all of them in order (Walk::next(j): the segment's next request, false at its
+// end) and the others do nothing.
+// The requests real traffic consists of — a live bucket, a request that does not reconfigure it — are answered by the closed forms of
+// guber_algo.h (a few dozen instructions).  Everything else goes through ONE inlined apply() site that serves both the rank-stepping
+// of a uniform run (eval_uniform_rank_1x's loop: run_step after every application) and the serial walk of a heterogeneous segment, so
+// a kernel carries the general state machine once, not four times — and the source carries this function once for both kernels.
+template <typename Walk>
+__device__ __forceinline__ void eval_core(const Table& T, const BatchView& B, const ResultView& R, const Work& W, const uint32_t i, const Req& r, const Rec& s0,
+                                          const uint32_t slot, const uint32_t rank, const uint32_t total, const bool parallel, Walk it,
+                                          int& c_over, int& c_hit, int& c_miss, int& c_size) {
+    Rec after; Resp out;
+    uint32_t ev = 0;
+    bool done = false;
+    if (parallel) {
+        if (token_fast_ok(s0, r, B.now_ms)) { ev = token_fast(s0, r, rank, out, after); done = true; }
+        else if (leaky_fast(s0, r, B.now_ms, rank, out, after, ev)) done = true;
+    }
+    const bool walk = !parallel && rank == 0;
+    uint32_t lastj = walk ? 0xffffffffu : i;                     // the run's last request (walk: the last one walked that reached the cache)
+    if ((parallel && !done) || walk) {
+        Req cur = r;
+        if (parallel) {                                          // the calendar values are loaded only here
+            if (B.greg_expire && B.greg_duration) { cur.greg_expire = B.greg_expire[i]; cur.greg_duration = B.greg_duration[i]; }
+            else if (cur.behavior & BH_GREGORIAN) greg_fill(B.now_ms, cur.duration, cur.greg_expire, cur.greg_duration, guber_tz());
+        }
+        after = s0;
+        uint64_t k = rank;
+        Rec prev2; rec_clear(prev2);
+        bool have_prev2 = false;
+        for (;;) {
+            uint32_t j = i;
+            if (walk) {
+                if (!it.next(j)) break;
+                cur = load_req(B, j);
+                if (cur.algorithm <= ALGO_LEAKY) lastj = j;
+            }
+            const Rec before = after;
+            const uint32_t e1 = apply(after, cur, B.now_ms, out);
+            if (walk) {
+                store_resp(R, j, out);
+                store_events(W, j, e1, after);
+                if (out.err == 0) queue_global(T, slot, cur, 1);
+                c_over += (e1 & EV_OVER) ? 1 : 0; c_hit += (e1 & EV_HIT) ? 1 : 0; c_miss += (e1 & EV_MISS) ? 1 : 0;
+                continue;
+            }
+            if (k == 0) { ev = e1; break; }
+            k--;
+            if (k == 0) continue;
+            run_step(before, after, prev2, have_prev2, k, cur, B.now_ms);
+        }
+    }
+    if (parallel) {
+        store_resp(R, i, out);
+        store_events(W, i, ev, after);
+        c_over = (ev & EV_OVER) ? 1 : 0; c_hit = (ev & EV_HIT) ? 1 : 0; c_miss = (ev & EV_MISS) ? 1 : 0;
+    }
+    // (a request with an invalid algorithm never reaches the cache — workers.go:317-321 rejects it before tokenBucket / leakyBucket call
+    // GetItem — so it does not move its key in the recency order: a run of such requests writes nothing, a walked segment is
+    // stamped with its last request that did reach the cache)
+    if ((parallel && rank == total - 1 && r.algorithm <= ALGO_LEAKY) || (walk && lastj != 0xffffffffu)) {
+        rec_set_stamp(after, W.touch + lastj);                // the key's place in the recency order: its last request (lrucache.go:111-128)
+        T.buckets[slot].rec = after;
+        c_size = (int)(rec_kind(after) != K_ABSENT) - (int)(rec_kind(s0) != K_ABSENT);
+        if (parallel && out.err == 0) queue_global(T, slot, r, (uint64_t)rank + 1);
+    }
+}
+
+// event counters of the workgroup (cnt: 4 LDS words zeroed by the caller): wave-level sums, one LDS atomic per wave and counter, one
+// barrier (zeroed_unsynced: a second one first, for a caller that has had no barrier since it zeroed cnt)
+__device__ __forceinline__ void eval_counters(const Table& T, const uint32_t tile, unsigned long long* cnt, const bool zeroed_unsynced,
+                                              const int c_over, const int c_hit, const int c_miss, const int c_size) {
+    const int w_over = wave_sum(c_over), w_hit = wave_sum(c_hit), w_miss = wave_sum(c_miss), w_size = wave_sum(c_size);
+    if (zeroed_unsynced) lds_barrier();
+    if ((threadIdx.x & 63) == 0 && (w_over | w_hit | w_miss | w_size)) {
+        if (w_over) atomicAdd(&cnt[0], (unsigned long long)w_over);
+        if (w_hit) atomicAdd(&cnt[1], (unsigned long long)w_hit);
+        if (w_miss) atomicAdd(&cnt[2], (unsigned long long)w_miss);
+        if (w_size) atomicAdd(&cnt[3], (unsigned long long)(long long)w_size);
+    }
+    lds_barrier();
+    if (threadIdx.x == 0 && (cnt[0] | cnt[1] | cnt[2] | cnt[3])) {
+        BlockCounters* bc = &T.bctr[tile];
+        bc->over += cnt[0]; bc->hits += cnt[1]; bc->misses += cnt[2]; bc->size_delta += (long long)cnt[3];
+    }
+}
+
+// k_eval2's walk: the tiles holding segment d in order (its tile bitmap), inside a tile the packed words whose id is d
+struct Eval2Walk {
+    const BatchView& B; const Work& W; const unsigned long long* seg_mask; uint32_t d;
+    uint32_t wv = 0, mm = 0, tt = 0, q = FT;
+    __device__ __forceinline__ bool next(uint32_t& j) {
+        for (;;) {
+            if (q < FT && tt * FT + q < B.n) {
+                const uint32_t id = W.did[(size_t)tt * FT + q];
+                q++;
+                if ((id >> 16) == d) { j = tt * FT + q - 1u; return true; }
+            } else {
+                while (mm == 0u && wv < FT_WORDS) {
+                    mm = (uint32_t)seg_mask[(size_t)d * FT_WORDS + wv];
+                    if (wv == (d / FT >> 5)) mm |= 1u << (d / FT & 31);      // the claimer's tile is not published
+                    tt = wv * 32; wv++;
+                }
+                if (mm == 0u) return false;
+                const uint32_t bpos = (uint32_t)__ffs((int)mm) - 1u; mm &= mm - 1u; tt = (tt & ~31u) + bpos; q = 0;
+            }
+        }
+    }
+};
+
 #ifndef GUBER_EVAL2_WAVES
 #define GUBER_EVAL2_WAVES 4      // waves per SIMD the register allocation must allow (<= 128 VGPRs): 4 co-resident workgroups per CU
 #endif
@@ -569,23 +708,8 @@ __device__ __forceinline__ void eval2_body(const EvalArgs& A, const uint32_t til
     lds_barrier();
     GB_STAMP2(2);
     int c_over = 0, c_hit = 0, c_miss = 0, c_size = 0;
-    // the wave in which every request is the common case runs straight through the closed form (as k_eval3's does,
-    // guber_kernels_part.h: one ballot instead of the general path's cascade of divergent sections; the same steps, so the same results)
-    const bool plain = !live || (!(rf & RF_INSERTED) && sf == 0u && !(smeta & SM_HAS_INVALID) && token_fast_ok(s0, r, B.now_ms));
-    const bool plain_wave = !W.store_flags && !T.gpend && __ballot(!plain) == 0ull;
-    if (plain_wave) {
-        if (live) {
-            const uint32_t total = stotal[lr >> 8], rank = sbase[lr >> 8] + (lr & 0xffu);
-            Rec after; Resp out;
-            const uint32_t ev = token_fast(s0, r, rank, out, after);
-            store_resp(R, i, out);
-            c_over = (ev & EV_OVER) ? 1 : 0; c_hit = (ev & EV_HIT) ? 1 : 0; c_miss = (ev & EV_MISS) ? 1 : 0;
-            if (rank == total - 1) {
-                rec_set_stamp(after, W.touch + i);                    // the key's place in the recency order: its last request (lrucache.go:111-128)
-                T.buckets[slot].rec = after;
-                c_size = (int)(rec_kind(after) != K_ABSENT) - (int)(rec_kind(s0) != K_ABSENT);
-            }
-        }
+    if (eval_plain_wave(T, B, W, live, (rf & RF_INSERTED) != 0, sf, smeta, s0, r)) {
+        if (live) eval_plain(T, R, W, i, r, s0, slot, sbase[lr >> 8] + (lr & 0xffu), stotal[lr >> 8], c_over, c_hit, c_miss, c_size);
     } else if (live) {
         if (rf & RF_INSERTED) atomicOr(&T.dir[W.slot[i]].meta, META_READY);   // publish this batch's inserts
         if (sf & SEG_ERR) {
@@ -595,8 +719,7 @@ __device__ __forceinline__ void eval2_body(const EvalArgs& A, const uint32_t til
             atomicAdd(&T.ctr->retries, 1ull);
         } else {
             if (smeta & SM_HAS_INVALID) s0.invalid_at = W.sinv[d];
-            const uint32_t base = sbase[lr >> 8], total = stotal[lr >> 8];
-            const uint32_t rank = base + (lr & 0xffu);
+            const uint32_t rank = sbase[lr >> 8] + (lr & 0xffu), total = stotal[lr >> 8];
             // requests differing only in created_at still take the parallel path when created_at cannot matter: live
             // token bucket (never read), or live leaky bucket where no request of the run leaks (the other members
             // were checked in k_front; the claimer's created_at is checked here, identically by every member)
@@ -611,122 +734,11 @@ __device__ __forceinline__ void eval2_body(const EvalArgs& A, const uint32_t til
                     parallel = created_at_irrelevant(s0, r, B.now_ms);
                 }
             }
-            // The requests real traffic consists of — a live bucket, a request that does not reconfigure it — are answered by
-            // the closed forms of guber_algo.h (a few dozen instructions).  Everything else goes through ONE inlined
-            // apply() site that serves both the rank-stepping of a uniform run (eval_uniform_rank_1x) and the serial walk
-            // of a heterogeneous segment, so the kernel carries the general state machine once, not four times.
-            Rec after; Resp out;
-            uint32_t ev = 0;
-            bool done = false;
-            if (parallel) {
-                if (token_fast_ok(s0, r, B.now_ms)) { ev = token_fast(s0, r, rank, out, after); done = true; }
-                else if (leaky_fast(s0, r, B.now_ms, rank, out, after, ev)) done = true;
-            }
-            const bool walk = !parallel && rank == 0;
-            uint32_t lastj = walk ? 0xffffffffu : i;                     // the run's last request (walk: the last one walked that reached the cache)
-            if ((parallel && !done) || walk) {
-                Req cur = r;
-                if (parallel) {                                          // the calendar values are loaded only here
-                    if (B.greg_expire && B.greg_duration) { cur.greg_expire = B.greg_expire[i]; cur.greg_duration = B.greg_duration[i]; }
-                    else if (cur.behavior & BH_GREGORIAN) greg_fill(B.now_ms, cur.duration, cur.greg_expire, cur.greg_duration, guber_tz());
-                }
-                after = s0;
-                uint64_t k = rank;
-                Rec prev2; rec_clear(prev2);
-                bool have_prev2 = false;
-                // walk iterator: tiles holding the segment in order (bitmap), inside a tile the packed words whose id is d
-                uint32_t wv = 0, mm = 0, tt = 0, q = FT;
-                for (;;) {
-                    uint32_t j = i;
-                    if (walk) {
-                        bool found = false, end = false;
-                        while (!found && !end) {
-                            if (q < FT && tt * FT + q < B.n) {
-                                const uint32_t id = W.did[(size_t)tt * FT + q];
-                                if ((id >> 16) == d) { j = tt * FT + q; found = true; }
-                                q++;
-                            } else {
-                                while (mm == 0u && wv < FT_WORDS) {
-                                    mm = (uint32_t)seg_mask[(size_t)d * FT_WORDS + wv];
-                                    if (wv == (d / FT >> 5)) mm |= 1u << (d / FT & 31);      // the claimer's tile is not published
-                                    tt = wv * 32; wv++;
-                                }
-                                if (mm == 0u) end = true;
-                                else { const uint32_t bpos = (uint32_t)__ffs((int)mm) - 1u; mm &= mm - 1u; tt = (tt & ~31u) + bpos; q = 0; }
-                            }
-                        }
-                        if (end) break;
-                        cur = load_req(B, j);
-                        if (cur.algorithm <= ALGO_LEAKY) lastj = j;
-                    }
-                    const Rec before = after;
-                    const uint32_t e1 = apply(after, cur, B.now_ms, out);
-                    if (walk) {
-                        store_resp(R, j, out);
-                        store_events(W, j, e1, after);
-                        if (out.err == 0) queue_global(T, slot, cur, 1);
-                        c_over += (e1 & EV_OVER) ? 1 : 0; c_hit += (e1 & EV_HIT) ? 1 : 0; c_miss += (e1 & EV_MISS) ? 1 : 0;
-                        continue;
-                    }
-                    if (k == 0) { ev = e1; break; }
-                    k--;
-                    if (k == 0) continue;
-                    if (rec_eq(after, before)) { k = 0; continue; }                       // fixed point
-                    if (have_prev2 && rec_eq(after, prev2)) {                             // period 2
-                        if (k & 1) after = before;
-                        k = 0;
-                        continue;
-                    }
-                    prev2 = before; have_prev2 = true;
-                    if (pure_subtract(before, after, cur, B.now_ms)) {
-                        const uint32_t kind = rec_kind(after);
-                        const int64_t n = kind == K_TOKEN ? after.remaining : go_f2i(bits2f(after.remaining));
-                        if (n > 0) {
-                            const uint64_t m = (uint64_t)(n - 1) / (uint64_t)cur.hits;
-                            const uint64_t jj = m < k ? m : k;
-                            if (jj > 0) {
-                                const int64_t dec = (int64_t)(jj * (uint64_t)cur.hits);   // <= n-1, exact
-                                if (kind == K_TOKEN) after.remaining -= dec;
-                                else after.remaining = f2bits(bits2f(after.remaining) - (double)dec);
-                                k -= jj;
-                                have_prev2 = false;
-                            }
-                        }
-                    }
-                }
-            }
-            if (parallel) {
-                store_resp(R, i, out);
-                store_events(W, i, ev, after);
-                c_over = (ev & EV_OVER) ? 1 : 0; c_hit = (ev & EV_HIT) ? 1 : 0; c_miss = (ev & EV_MISS) ? 1 : 0;
-            }
-            // (a request with an invalid algorithm never reaches the cache — workers.go:317-321 rejects it before tokenBucket / leakyBucket call
-            // GetItem — so it does not move its key in the recency order: a run of such requests writes nothing, a walked segment is
-            // stamped with its last request that did reach the cache)
-            if ((parallel && rank == total - 1 && r.algorithm <= ALGO_LEAKY) || (walk && lastj != 0xffffffffu)) {
-                rec_set_stamp(after, W.touch + lastj);                // the key's place in the recency order: its last request (lrucache.go:111-128)
-                T.buckets[slot].rec = after;
-                c_size = (int)(rec_kind(after) != K_ABSENT) - (int)(rec_kind(s0) != K_ABSENT);
-                if (parallel && out.err == 0) queue_global(T, slot, r, (uint64_t)rank + 1);
-            }
+            eval_core(T, B, R, W, i, r, s0, slot, rank, total, parallel, Eval2Walk{B, W, seg_mask, d}, c_over, c_hit, c_miss, c_size);
         }
     }
     GB_STAMP2(3);
-    // event counters of the workgroup: wave-level sums, one LDS atomic per wave and counter, one barrier
-    {
-        const int w_over = wave_sum(c_over), w_hit = wave_sum(c_hit), w_miss = wave_sum(c_miss), w_size = wave_sum(c_size);
-        if ((threadIdx.x & 63) == 0 && (w_over | w_hit | w_miss | w_size)) {
-            if (w_over) atomicAdd(&cnt[0], (unsigned long long)w_over);
-            if (w_hit) atomicAdd(&cnt[1], (unsigned long long)w_hit);
-            if (w_miss) atomicAdd(&cnt[2], (unsigned long long)w_miss);
-            if (w_size) atomicAdd(&cnt[3], (unsigned long long)(long long)w_size);
-        }
-        lds_barrier();
-        if (threadIdx.x == 0 && (cnt[0] | cnt[1] | cnt[2] | cnt[3])) {
-            BlockCounters* bc = &T.bctr[tile];
-            bc->over += cnt[0]; bc->hits += cnt[1]; bc->misses += cnt[2]; bc->size_delta += (long long)cnt[3];
-        }
-    }
+    eval_counters(T, tile, cnt, false, c_over, c_hit, c_miss, c_size);
     GB_STAMP2(4);
 }
 // (the arguments are read through the kernel-argument pointer, as k_eval2_multi does: preloading all of them into scalar registers
@@ -776,18 +788,23 @@ __device__ __forceinline__ uint32_t multi_batch_of(const uint32_t* ends, uint32_
     for (int k = 0; k < N - 1; ++k) first = sb == (uint32_t)(k + 1) ? e[k] : first;
     return sb;
 }
+// ... and that batch's argument block: entry sb of the array that lies sub_offset bytes into the kernel-argument segment (addressed
+// from the segment pointer itself, so that the block is read with scalar loads like any kernel argument)
+template <int N, typename Sub>
+__device__ __forceinline__ const Sub* multi_sub_of(const uint32_t* ends, const size_t sub_offset, const uint32_t wg, uint32_t& first, uint32_t& sb) {
+    sb = multi_batch_of<N>(ends, wg, first);
+    return (const Sub*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + sub_offset) + sb;
+}
 __global__ __launch_bounds__(FT) void k_front_multi(MultiFront A) {
     const MultiFront* m = (const MultiFront*)__builtin_amdgcn_kernarg_segment_ptr();
-    uint32_t first;
-    const uint32_t sb = multi_batch_of<MULTI_MAX>(m->end_tile, blockIdx.x, first);
-    const FrontArgs* a = (const FrontArgs*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(MultiFront, sub)) + sb;
+    uint32_t first, sb;
+    const FrontArgs* a = multi_sub_of<MULTI_MAX, FrontArgs>(m->end_tile, offsetof(MultiFront, sub), blockIdx.x, first, sb);
     front_body(a->T, a->B, a->W, blockIdx.x - first);
 }
 __global__ __launch_bounds__(256, GUBER_EVAL2_WAVES) void k_eval2_multi(MultiEval A) {
     const MultiEval* m = (const MultiEval*)__builtin_amdgcn_kernarg_segment_ptr();
-    uint32_t first;
-    const uint32_t sb = multi_batch_of<MULTI_MAX>(m->end_tile, blockIdx.x, first);
-    const EvalArgs* a = (const EvalArgs*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(MultiEval, sub)) + sb;
+    uint32_t first, sb;
+    const EvalArgs* a = multi_sub_of<MULTI_MAX, EvalArgs>(m->end_tile, offsetof(MultiEval, sub), blockIdx.x, first, sb);
     eval2_body(*a, blockIdx.x - first, m->end_tile[sb] - first);
 }
 

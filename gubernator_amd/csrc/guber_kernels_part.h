@@ -747,6 +747,26 @@ __global__ __launch_bounds__(256, GUBER_OWN_WAVES) void k_own(Table T, BatchView
 // before the evaluation.  The serial walk of a heterogeneous segment follows the segment's tile map (Work::segtiles, tilerow).
 // (Measured and not kept, round 4: the closed forms and the rest as two launches — the first at eight waves per SIMD: +1 % / -7 %,
 // profiles/r04_split_eval3_ab.txt.)
+
+// the walk's iterator (eval_core): the tiles holding segment d in order (its tile map, read as 8 x 32 tiles), inside a tile the requests of the segment's group
+struct Eval3Walk {
+    const BatchView& B; const Work& W; uint32_t d;
+    uint32_t wv = 0, mm = 0, tt = 0, q = FT, tj = 0;
+    __device__ __forceinline__ bool next(uint32_t& j) {
+        for (;;) {
+            if (q < FT && tt * FT + q < B.n) {
+                const uint32_t id = W.did[(size_t)tt * FT + q];
+                q++;
+                if ((id & 0xffu) == tj && ((id >> 16) & 0xffu) == 0u) { j = tt * FT + q - 1u; return true; }
+            } else {
+                while (mm == 0u && wv < 8) { mm = ((const uint32_t*)W.segtiles)[(size_t)d * 8 + wv]; tt = wv * 32; wv++; }
+                if (mm == 0u) return false;
+                const uint32_t bpos = (uint32_t)__ffs((int)mm) - 1u; mm &= mm - 1u; tt = (tt & ~31u) + bpos; q = 0;
+                tj = W.tilerow[(size_t)d * FT_MAX_TILES + tt];
+            }
+        }
+    }
+};
 __device__ __forceinline__ void eval3_body(const EvalArgs& A, const uint32_t tile) {
     const Table& T = A.T; const BatchView& B = A.B; const ResultView& R = A.R; const Work& W = A.W;
     __shared__ unsigned long long cnt[4];
@@ -790,26 +810,8 @@ __device__ __forceinline__ void eval3_body(const EvalArgs& A, const uint32_t til
     if (threadIdx.x < 4) cnt[threadIdx.x] = 0ull;
     GP_STAMPW(2, 1);
     int c_over = 0, c_hit = 0, c_miss = 0, c_size = 0;
-    // The wave in which EVERY request is the common case — a live token bucket met by a request that does not reconfigure it, nothing
-    // flagged, no Store side channel, no GLOBAL bookkeeping — runs straight through the closed form: one ballot instead of the general
-    // path's cascade of divergent branches (error codes, flags, the leaky form, the serial walk, events, queues), each of which costs
-    // every wave its exec-mask bookkeeping whether a lane takes it or not.  Exactly the general path's own steps for such a request
-    // (token_fast_ok -> token_fast -> store -> the run's last request writes the bucket), so the results are the same by construction.
-    const bool plain = !live || (!derr && sf == 0u && !(smeta & SM_HAS_INVALID) && token_fast_ok(s0, r, B.now_ms));
-    const bool plain_wave = !W.store_flags && !T.gpend && __ballot(!plain) == 0ull;
-    if (plain_wave) {
-        if (live) {
-            const uint32_t rank = base + lr;
-            Rec after; Resp out;
-            const uint32_t ev = token_fast(s0, r, rank, out, after);
-            store_resp(R, i, out);
-            c_over = (ev & EV_OVER) ? 1 : 0; c_hit = (ev & EV_HIT) ? 1 : 0; c_miss = (ev & EV_MISS) ? 1 : 0;
-            if (rank == total - 1) {
-                rec_set_stamp(after, W.touch + i);                    // the key's place in the recency order: its last request (lrucache.go:111-128)
-                T.buckets[slot].rec = after;
-                c_size = (int)(rec_kind(after) != K_ABSENT) - (int)(rec_kind(s0) != K_ABSENT);
-            }
-        }
+    if (eval_plain_wave(T, B, W, live, derr != 0u, sf, smeta, s0, r)) {
+        if (live) eval_plain(T, R, W, i, r, s0, slot, base + lr, total, c_over, c_hit, c_miss, c_size);
     } else if (live) {
         const uint32_t rank = base + lr;
         const bool flagged = (sf & (SEG_NONUNIFORM | SEG_CREATED_DIFFERS)) != 0u;
@@ -829,99 +831,7 @@ __device__ __forceinline__ void eval3_body(const EvalArgs& A, const uint32_t til
                 parallel = !(T.gpend && (r.behavior & BH_GLOBAL));
                 if (parallel && r.algorithm != ALGO_LEAKY) parallel = created_at_irrelevant(s0, r, B.now_ms);
             }
-            Rec after; Resp out;
-            uint32_t ev = 0;
-            bool done = false;
-            if (parallel) {
-                if (token_fast_ok(s0, r, B.now_ms)) { ev = token_fast(s0, r, rank, out, after); done = true; }
-                else if (leaky_fast(s0, r, B.now_ms, rank, out, after, ev)) done = true;
-            }
-            const bool walk = !parallel && rank == 0;
-            uint32_t lastj = walk ? 0xffffffffu : i;                     // the run's last request (walk: the last one walked that reached the cache)
-            if ((parallel && !done) || walk) {
-                Req cur = r;
-                if (parallel) {                                          // the calendar values are loaded only here
-                    if (B.greg_expire && B.greg_duration) { cur.greg_expire = B.greg_expire[i]; cur.greg_duration = B.greg_duration[i]; }
-                    else if (cur.behavior & BH_GREGORIAN) greg_fill(B.now_ms, cur.duration, cur.greg_expire, cur.greg_duration, guber_tz());
-                }
-                after = s0;
-                uint64_t k = rank;
-                Rec prev2; rec_clear(prev2);
-                bool have_prev2 = false;
-                // walk iterator: the tiles holding the segment in order (its tile map), inside a tile the requests of the segment's group
-                uint32_t wv = 0, tt = 0, q = FT, tj = 0, mm = 0u;          // (the map read as 8 x 32 tiles)
-                for (;;) {
-                    uint32_t j = i;
-                    if (walk) {
-                        bool found = false, end = false;
-                        while (!found && !end) {
-                            if (q < FT && tt * FT + q < B.n) {
-                                const uint32_t id = W.did[(size_t)tt * FT + q];
-                                if ((id & 0xffu) == tj && ((id >> 16) & 0xffu) == 0u) { j = tt * FT + q; found = true; }
-                                q++;
-                            } else {
-                                while (mm == 0u && wv < 8) { mm = ((const uint32_t*)W.segtiles)[(size_t)d * 8 + wv]; tt = wv * 32; wv++; }
-                                if (mm == 0u) end = true;
-                                else {
-                                    const uint32_t bpos = (uint32_t)__ffs((int)mm) - 1u; mm &= mm - 1u; tt = (tt & ~31u) + bpos; q = 0;
-                                    tj = W.tilerow[(size_t)d * FT_MAX_TILES + tt];
-                                }
-                            }
-                        }
-                        if (end) break;
-                        cur = load_req(B, j);
-                        if (cur.algorithm <= ALGO_LEAKY) lastj = j;
-                    }
-                    const Rec before = after;
-                    const uint32_t e1 = apply(after, cur, B.now_ms, out);
-                    if (walk) {
-                        store_resp(R, j, out);
-                        store_events(W, j, e1, after);
-                        if (out.err == 0) queue_global(T, slot, cur, 1);
-                        c_over += (e1 & EV_OVER) ? 1 : 0; c_hit += (e1 & EV_HIT) ? 1 : 0; c_miss += (e1 & EV_MISS) ? 1 : 0;
-                        continue;
-                    }
-                    if (k == 0) { ev = e1; break; }
-                    k--;
-                    if (k == 0) continue;
-                    if (rec_eq(after, before)) { k = 0; continue; }                       // fixed point
-                    if (have_prev2 && rec_eq(after, prev2)) {                             // period 2
-                        if (k & 1) after = before;
-                        k = 0;
-                        continue;
-                    }
-                    prev2 = before; have_prev2 = true;
-                    if (pure_subtract(before, after, cur, B.now_ms)) {
-                        const uint32_t kind = rec_kind(after);
-                        const int64_t n = kind == K_TOKEN ? after.remaining : go_f2i(bits2f(after.remaining));
-                        if (n > 0) {
-                            const uint64_t m = (uint64_t)(n - 1) / (uint64_t)cur.hits;
-                            const uint64_t jj = m < k ? m : k;
-                            if (jj > 0) {
-                                const int64_t dec = (int64_t)(jj * (uint64_t)cur.hits);   // <= n-1, exact
-                                if (kind == K_TOKEN) after.remaining -= dec;
-                                else after.remaining = f2bits(bits2f(after.remaining) - (double)dec);
-                                k -= jj;
-                                have_prev2 = false;
-                            }
-                        }
-                    }
-                }
-            }
-            if (parallel) {
-                store_resp(R, i, out);
-                store_events(W, i, ev, after);
-                c_over = (ev & EV_OVER) ? 1 : 0; c_hit = (ev & EV_HIT) ? 1 : 0; c_miss = (ev & EV_MISS) ? 1 : 0;
-            }
-            // (a request with an invalid algorithm never reaches the cache — workers.go:317-321 rejects it before tokenBucket / leakyBucket call
-            // GetItem — so it does not move its key in the recency order: a run of such requests writes nothing, a walked segment is
-            // stamped with its last request that did reach the cache)
-            if ((parallel && rank == total - 1 && r.algorithm <= ALGO_LEAKY) || (walk && lastj != 0xffffffffu)) {
-                rec_set_stamp(after, W.touch + lastj);                // the key's place in the recency order: its last request (lrucache.go:111-128)
-                T.buckets[slot].rec = after;
-                c_size = (int)(rec_kind(after) != K_ABSENT) - (int)(rec_kind(s0) != K_ABSENT);
-                if (parallel && out.err == 0) queue_global(T, slot, r, (uint64_t)rank + 1);
-            }
+            eval_core(T, B, R, W, i, r, s0, slot, rank, total, parallel, Eval3Walk{B, W, d}, c_over, c_hit, c_miss, c_size);
         }
         // the first request of a segment that carries a tile map clears it (walked or not): the map is all zero between batches
         if (!derr && flagged && rank == 0) {
@@ -930,21 +840,7 @@ __device__ __forceinline__ void eval3_body(const EvalArgs& A, const uint32_t til
         }
     }
     GP_STAMP(2, 2);
-    {
-        const int w_over = wave_sum(c_over), w_hit = wave_sum(c_hit), w_miss = wave_sum(c_miss), w_size = wave_sum(c_size);
-        lds_barrier();                                               // (cnt zeroed)
-        if ((threadIdx.x & 63) == 0 && (w_over | w_hit | w_miss | w_size)) {
-            if (w_over) atomicAdd(&cnt[0], (unsigned long long)w_over);
-            if (w_hit) atomicAdd(&cnt[1], (unsigned long long)w_hit);
-            if (w_miss) atomicAdd(&cnt[2], (unsigned long long)w_miss);
-            if (w_size) atomicAdd(&cnt[3], (unsigned long long)(long long)w_size);
-        }
-        lds_barrier();
-        if (threadIdx.x == 0 && (cnt[0] | cnt[1] | cnt[2] | cnt[3])) {
-            BlockCounters* bc = &T.bctr[tile];
-            bc->over += cnt[0]; bc->hits += cnt[1]; bc->misses += cnt[2]; bc->size_delta += (long long)cnt[3];
-        }
-    }
+    eval_counters(T, tile, cnt, true, c_over, c_hit, c_miss, c_size);     // (cnt was zeroed without a barrier: this kernel has none before the evaluation)
     // the owner count of the next batch (all of this batch's k_own workgroups are done, the next batch's k_part has not started)
     if (tile == 0 && threadIdx.x == 0) {
         uint32_t* pm = W.pmode;
@@ -968,9 +864,8 @@ __global__ __launch_bounds__(256, GUBER_EVAL2_WAVES) void k_eval3(EvalArgs A) {
 // kernel arguments; k_own_multi: 256 owners per batch, so that an owner's XCD is the same in every batch) ----------------------
 __global__ __launch_bounds__(FT, GUBER_PART_WAVES) void k_part_multi(MultiFront A) {
     const MultiFront* m = (const MultiFront*)__builtin_amdgcn_kernarg_segment_ptr();
-    uint32_t first;
-    const uint32_t sb = multi_batch_of<MULTI_MAX>(m->end_tile, blockIdx.x, first);
-    const FrontArgs* a = (const FrontArgs*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(MultiFront, sub)) + sb;
+    uint32_t first, sb;
+    const FrontArgs* a = multi_sub_of<MULTI_MAX, FrontArgs>(m->end_tile, offsetof(MultiFront, sub), blockIdx.x, first, sb);
     part_body(a->T, a->B, a->W, blockIdx.x - first);
 }
 __global__ __launch_bounds__(256, GUBER_OWN_WAVES) void k_own_multi(MultiFront A) {
@@ -982,9 +877,8 @@ __global__ __launch_bounds__(256, GUBER_OWN_WAVES) void k_own_multi(MultiFront A
 }
 __global__ __launch_bounds__(256, GUBER_EVAL2_WAVES) void k_eval3_multi(MultiEval A) {
     const MultiEval* m = (const MultiEval*)__builtin_amdgcn_kernarg_segment_ptr();
-    uint32_t first;
-    const uint32_t sb = multi_batch_of<MULTI_MAX>(m->end_tile, blockIdx.x, first);
-    const EvalArgs* a = (const EvalArgs*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(MultiEval, sub)) + sb;
+    uint32_t first, sb;
+    const EvalArgs* a = multi_sub_of<MULTI_MAX, EvalArgs>(m->end_tile, offsetof(MultiEval, sub), blockIdx.x, first, sb);
     eval3_body(*a, blockIdx.x - first);
 }
 
@@ -1014,9 +908,8 @@ __global__ __launch_bounds__(256, GUBER_EVAL2_WAVES) void k_evalpart_multi(Multi
     const uint32_t tiles_e = m->end_e[m->nb - 1];
     const bool part = blockIdx.x >= tiles_e;
     const uint32_t wg = part ? blockIdx.x - tiles_e : blockIdx.x;
-    uint32_t first;
-    const uint32_t sb = multi_batch_of<EP_MAX>(part ? m->end_p : m->end_e, wg, first);
-    const EPSub* a = (const EPSub*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(MultiEP, sub)) + sb;
+    uint32_t first, sb;
+    const EPSub* a = multi_sub_of<EP_MAX, EPSub>(part ? m->end_p : m->end_e, offsetof(MultiEP, sub), wg, first, sb);
     if (!part) { eval3_body(a->E, wg - first); return; }
     Work W = a->E.W;                                       // the next batch's work arrays are this engine's, but for:
     W.did = a->did_p; W.pmslot = a->pmslot_p;

@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import eval_runs
 import gubernator_amd as ga
 import scenarios
 import streams
@@ -111,6 +112,34 @@ def test_adversarial_streams(seed, flags):
         want, got = o.eval(b), e.eval(b)
         support.assert_results_equal(got, want, f"seed {seed} batch {bi}")
         assert got.counters() == want.counters(), f"counters seed {seed} batch {bi}: {got.counters()} {want.counters()}"
+    e.close()
+
+
+@pytest.mark.parametrize("flags", [64, 128, 4, 2, 0])
+def test_runs_and_walks_the_closed_forms_decline(flags):
+    """tests/eval_runs.py (the CPU twin is in tests/test_kernels_devsim.py): uniform runs the closed forms decline, heterogeneous
+    segments, a walk across a word of the tile map — every batch, the 8 plain requests after it included, and the counters and the
+    size after it, bit-exact against the oracle.  With flags 0 the uniform cases once more in batches of 200: the one-launch path."""
+    o, e = Oracle(cache_size=1 << 16), engine(max_batch=eval_runs.WORD_N, flags=flags)
+    cases = eval_runs.all_cases(support.gregorian)
+    if flags == 0:
+        cases += eval_runs.uniform_cases(support.gregorian, eval_runs.SMALL_RUN, eval_runs.SMALL_OTHERS, now=eval_runs.NOW0 + 3000)
+    for label, batches in cases:
+        for k, b in enumerate(batches):
+            want, got = o.eval(b), e.eval(b)
+            support.assert_results_equal(got, want, f"flags {flags}: {label}, batch {k}")
+            assert got.counters() == want.counters(), f"flags {flags}: {label}, batch {k}: counters {got.counters()} {want.counters()}"
+            assert e.counters()[:3] == o.counters()[:3] and e.size() == o.size(), (flags, label, k, e.counters(), o.counters(), o.size())
+    e.close()
+    # the walked segment under a binding cache: the recency stamp it leaves decides who is evicted
+    cs = eval_runs.RECENCY_CACHE
+    o, e = Oracle(cache_size=cs), engine(cache_size=cs, max_batch=1024, flags=flags)
+    label, batches = eval_runs.recency_case()
+    for k, b in enumerate(batches):
+        want, got = o.eval(b), e.eval(b)
+        support.assert_results_equal(got, want, f"flags {flags}: {label}, batch {k}")
+        assert got.counters() == want.counters(), f"flags {flags}: {label}, batch {k}: counters {got.counters()} {want.counters()}"
+    assert e.stats()["unexpired_evictions"] == o.counters()[3] > 0 and e.size() == o.size()
     e.close()
 
 

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import eval_runs
 import streams
 from support import GREGORIAN, ROOT, GuberBatch, GuberResult, HostBatch, HostResult, Oracle, assert_results_equal, gregorian
 
@@ -110,6 +111,31 @@ def test_adversarial_streams_through_the_kernel_source(lib, pipeline, seed):
     assert retries == 0
     co = orc.counters()
     assert (o, hi, mi) == (co[0], co[1], co[2]) and sz == orc.size()
+    sim.close()
+
+
+@pytest.mark.parametrize("pipeline", [1, 0])
+def test_runs_and_walks_the_closed_forms_decline(lib, pipeline):
+    """tests/eval_runs.py: one key 600 times among 40 others with requests the closed forms decline (period 2, fixed point, stepping,
+    reconfigure / create then extrapolate, the calendar; each with DRAIN_OVER_LIMIT too), the serial walk (alternating hits with an
+    invalid algorithm last, created_at only), a run of invalid algorithms, and a walk over tiles 0, 31, 32, 33 of 34 — every batch,
+    the 8 plain requests after it included, the counters and the size equal to the oracle's; then the walked segment under a binding
+    cache, where the recency stamp it leaves decides who is evicted"""
+    only_where_the_form_matters(lib, pipeline)
+    sim, orc = Sim(lib, slots=1 << 15, max_batch=eval_runs.WORD_N, pipeline=pipeline), Oracle()
+    for label, batches in eval_runs.all_cases(gregorian):
+        for k, b in enumerate(batches):
+            assert_results_equal(sim.eval(b), orc.eval(b), f"{label}, batch {k}")
+            o, hi, mi, sz, retries, _ = sim.counters()
+            assert retries == 0 and (o, hi, mi) == orc.counters()[:3] and sz == orc.size(), (label, k, sim.counters(), orc.counters(), orc.size())
+    sim.close()
+    cs = eval_runs.RECENCY_CACHE
+    sim, orc = Sim(lib, slots=1 << 12, max_batch=1024, pipeline=pipeline, cache_size=cs), Oracle(cache_size=cs)
+    label, batches = eval_runs.recency_case()
+    for k, b in enumerate(batches):
+        assert_results_equal(sim.eval(b), orc.eval(b), f"{label}, batch {k}")
+        assert sim.counters()[:4] == orc.counters()[:3] + (orc.size(),), (label, k, sim.counters(), orc.counters(), orc.size())
+    assert sim.lru_stats()["unexpired_evictions"] == orc.counters()[3] > 0
     sim.close()
 
 

@@ -235,7 +235,7 @@ static int front_out(guber_front* f, guber_front::Slot& s, guber_result_t* r) {
     f->last_os = os;
     for (auto& h : s.hooks) if (h->st != os) HIPCHK(hipStreamWaitEvent(os, h->ev, 0));
     FrOut O{};
-    O.n = s.n; O.fwd = s.in.d_fwd;
+    O.n = s.n; O.er = s.in.er; O.tile_cnt = s.in.tile_cnt; O.tile_base = s.in.tile_base; O.ctl = s.in.ctl;   // (the slot's routing scratch: routed into again only behind ev_out)
     O.d_status = s.o_status; O.d_err = s.o_err; O.d_limit = s.o_limit; O.d_remaining = s.o_remaining; O.d_reset_time = s.o_reset;
     O.status = r->status; O.err = r->err; O.limit = r->limit; O.remaining = r->remaining; O.reset_time = r->reset_time;
     guber_engine* e0 = f->eng[0];
@@ -245,7 +245,7 @@ static int front_out(guber_front* f, guber_front::Slot& s, guber_result_t* r) {
     if (f->enc_hook) {
         // the payload stage (guber_wire_pool.h): the answers' last hop is the encoder — every RPC's GetRateLimitsResp bytes from the shares, through fwd
         guber::WireEnc E = *f->enc_hook;
-        E.fwd = O.fwd; E.d_status = O.d_status; E.d_err = O.d_err; E.d_limit = O.d_limit; E.d_remaining = O.d_remaining; E.d_reset = O.d_reset_time;
+        E.fwd = s.in.d_fwd; E.d_status = O.d_status; E.d_err = O.d_err; E.d_limit = O.d_limit; E.d_remaining = O.d_remaining; E.d_reset = O.d_reset_time;
         hipLaunchKernelGGL(guber::k_wire_enc, dim3(E.nrpc), dim3(guber::WE_T), 0, os, E);
     } else
     hipLaunchKernelGGL(k_fr_out, dim3((s.n + FR_TILE - 1u) / FR_TILE), dim3(256), 0, os, O);

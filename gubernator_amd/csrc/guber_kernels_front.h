@@ -14,10 +14,13 @@ namespace guber {
 //                 sizes to the host and releases the flag it polls
 //   k_fr_scatter  request i -> place d = base[engine] + tile_base + rank of the mirror: every engine's share is
 //                 contiguous and in arrival order (requests of one key keep their order), the fused pipelines run on the shares as
-//                 on any batch; fwd[i] = d.  Keys of ONE width (<= 32 bytes: every front end that formats its keys) travel with
-//                 their requests — share j's keys are packed, key_off[d] = d x width, so k_part's speculative key fetch applies —
+//                 on any batch; fwd[i] = d.  The tile is put into the shares' order in LDS first (the place there is computed:
+//                 lbase[engine] + rank), so consecutive threads store consecutive d of a run.  Keys of ONE width (<= 32 bytes:
+//                 every front end that formats its keys) travel with their requests as 8-byte words through the same LDS —
+//                 share j's keys are packed, key_off[d] = d x width, so k_part's speculative key fetch applies —
 //                 other keys stay where they are and the share carries offset + length (BatchView.key_len)
-//   k_fr_out      answer i = share answer fwd[i]: coalesced writes in arrival order
+//   k_fr_out      the same, mirrored: consecutive threads load consecutive share answers of a run, LDS, answer i from the place
+//                 er[i] gives: coalesced reads in the shares' order, coalesced writes in arrival order (fwd is not read)
 constexpr uint32_t FR_PER = 4;                     // requests per thread of the copy kernels
 constexpr uint32_t FR_TILE = 256 * FR_PER;         // requests per tile
 constexpr uint32_t FR_RANK_BITS = 10;              // er[i] = engine << 10 | rank among the tile's requests of that engine
@@ -64,8 +67,8 @@ __device__ __forceinline__ uint32_t fr_len0(const FrIn& A) { return A.key_stride
 // took 157 us for 524 288 requests with nothing else on the GPU).
 // A tile is FR_TILE = 1 024 requests (round 6's second form; the first had 256): a generation has a quarter of the tiles and scan
 // steps, and the runs the copy kernels move (a tile's requests of one engine, consecutive in the share) are four times as long — about
-// 85 elements with twelve engines: sectors are used almost fully.  k_fr_scatter / k_fr_out take four requests per thread (request k of
-// thread t: tile x 1024 + k x 256 + t — coalesced, every load before the first store).
+// 85 elements with twelve engines.  k_fr_scatter / k_fr_out take four requests per thread (request k of thread t: tile x 1024 + k x 256 + t
+// on the arrival side, sorted element k x 256 + t on the shares' side — both coalesced; see "the copy kernels" below).
 __global__ __launch_bounds__(FR_TILE) void k_fr_count(FrIn A) {
     // one request per thread, 1 024 threads: the chain offsets -> key -> hot-key list -> slot table is four dependent trips, and what hides
     // them is waves in flight (four requests per thread, a quarter of the waves: 24 us instead of 20 for a million requests)
@@ -155,77 +158,198 @@ __global__ __launch_bounds__(FR_SCAN_T) void k_fr_scan(FrIn A, uint32_t nt, uint
     }
 }
 
-__global__ __launch_bounds__(256) void k_fr_scatter(FrIn A) {
-    __shared__ uint32_t sbase[MULTI_MEM_MAX];                        // where each engine's share starts: the prefix over the shares' sizes
-    if (threadIdx.x < MULTI_MEM_MAX) {
-        uint32_t b = 0;
-        for (uint32_t k = 0; k < threadIdx.x; ++k) b += A.ctl->tot[k];
-        sbase[threadIdx.x] = b;
+// ---- the copy kernels: a tile is put into the shares' order in LDS, so that consecutive threads move consecutive elements of a run ------
+// A tile's requests of engine e are one RUN of the share: tile_cnt[tile][e] consecutive places from sbase[e] + tile_base[tile][e], in
+// arrival order.  Sorted by engine (stable), the tile's request i = (e, rank) has the local place p = lbase[e] + rank — lbase the exclusive
+// prefix of the tile's sixteen counts: computed, never searched for — and sorted element j lies at d = dofs[e] + j of the mirror, dofs[e] =
+// sbase[e] + tile_base[tile][e] - lbase[e].  A column goes through LDS: arrival order on the side of the caller's arrays (thread t:
+// t, t + 256, ... — coalesced), sorted order on the side of the shares (thread t: sorted elements t, t + 256, ... — consecutive d inside a
+// run: a wave's access covers whole sectors except at the ends of the dozen runs it touches; before, lane by lane in arrival order, every
+// access of every column fell into a dozen runs of about five elements each).
+struct FrTile { uint32_t lbase[MULTI_MEM_MAX + 1], dofs[MULTI_MEM_MAX]; };
+// sixteen threads: the places of the shares (the prefix over the shares' sizes) and of the tile's runs; the workgroup meets behind it
+__device__ __forceinline__ void fr_tile_bases(FrTile& T, const FrontCtl* ctl, const uint32_t* tile_cnt, const uint32_t* tile_base, uint32_t tile) {
+    const uint32_t e = threadIdx.x;
+    if (e < MULTI_MEM_MAX) {
+        const uint32_t* cnt = tile_cnt + (size_t)tile * MULTI_MEM_MAX;
+        uint32_t s = 0, l = 0;
+        for (uint32_t k = 0; k < e; ++k) { s += ctl->tot[k]; l += cnt[k]; }
+        T.lbase[e] = l; T.dofs[e] = s + tile_base[(size_t)tile * MULTI_MEM_MAX + e] - l;
+        if (e == MULTI_MEM_MAX - 1) T.lbase[MULTI_MEM_MAX] = l + cnt[e];
     }
     __syncthreads();
-    const uint32_t tile = blockIdx.x, i0 = tile * FR_TILE + threadIdx.x;
-    const bool packed = A.ctl->ragged_seq != A.seq;                   // keys of one width: they travel with their requests
-    uint32_t er[FR_PER], o0[FR_PER], o1[FR_PER], beh[FR_PER]; int64_t hits[FR_PER], limit[FR_PER], duration[FR_PER]; uint8_t algo[FR_PER];
+}
+// the engine of sorted element j < lbase[16]: the LAST one whose run starts at or before j (engines without requests in the tile have
+// the lbase of their successor: counting the starts <= j steps over them) — fifteen compares, no loop over memory
+__device__ __forceinline__ uint32_t fr_engine_of(const FrTile& T, uint32_t j) {
+    uint32_t e = 0;
 #pragma unroll
-    for (int k = 0; k < FR_PER; ++k) {                               // every load of the thread's four requests before the first store
-        const uint32_t i = i0 + k * 256u;
-        if (i >= A.n) { er[k] = 0xffffffffu; continue; }
-        er[k] = A.er[i]; o0[k] = fr_key_off(A, i); o1[k] = o0[k] + fr_key_len(A, i, o0[k]);
-        hits[k] = A.hits[i]; limit[k] = A.limit[i]; duration[k] = A.duration[i];
-        beh[k] = A.behavior ? A.behavior[i] : 0u; algo[k] = A.algorithm ? A.algorithm[i] : (uint8_t)0;
-    }
+    for (uint32_t q = 1; q < MULTI_MEM_MAX; ++q) e += T.lbase[q] <= j ? 1u : 0u;
+    return e;
+}
+// the mirror's place of the thread's sorted elements (0xffffffff: behind the tile's last request)
+__device__ __forceinline__ void fr_sorted_places(const FrTile& T, uint32_t n, uint32_t (&dd)[FR_PER]) {
+    const uint32_t cnt = T.lbase[MULTI_MEM_MAX] < FR_TILE ? T.lbase[MULTI_MEM_MAX] : FR_TILE;
 #pragma unroll
     for (int k = 0; k < FR_PER; ++k) {
-        const uint32_t i = i0 + k * 256u;
-        if (er[k] == 0xffffffffu) continue;
-        const uint32_t e = er[k] >> FR_RANK_BITS, rank = er[k] & ((1u << FR_RANK_BITS) - 1u);
-        const uint32_t d = sbase[e] + A.tile_base[tile * MULTI_MEM_MAX + e] + rank;
-        A.d_fwd[i] = d < A.n ? d : 0u;
-        if (d >= A.n) continue;                                      // (cannot happen: the ranks are a permutation; nothing is written out of bounds)
-        A.d_hits[d] = hits[k]; A.d_limit[d] = limit[k]; A.d_duration[d] = duration[k]; A.d_behavior[d] = beh[k]; A.d_algorithm[d] = algo[k];
-        if (A.burst) A.d_burst[d] = A.burst[i];
-        if (A.created_at) A.d_created_at[d] = A.created_at[i];
-        if (A.is_owner) A.d_is_owner[d] = A.is_owner[i];
-        if (packed) {
-            const uint32_t len = o1[k] - o0[k];
-            const uint8_t* src = A.key_bytes + o0[k]; uint8_t* dst = A.d_keys + (size_t)d * len;
-            if (len >= 8) {                                          // whole words, the last one overlapping the one before: nothing is written behind the
-                uint32_t b = 0;                                      // key, whose neighbour's first bytes are another thread's
-                for (; b + 8 <= len; b += 8) { const uint64_t w = ld_key_word(src + b); __builtin_memcpy(dst + b, &w, 8); }
-                if (b < len) { const uint64_t w = ld_key_word(src + len - 8); __builtin_memcpy(dst + len - 8, &w, 8); }
-            } else {
-                const uint64_t w = ld_key_word(src);                 // (a key buffer is readable 8 bytes past its last key)
-                for (uint32_t q = 0; q < len; ++q) dst[q] = (uint8_t)(w >> (8 * q));
-            }
-            A.d_key_off[d] = d * len;
-            if (d == A.n - 1) A.d_key_off[A.n] = A.n * len;
-        } else {
-            A.d_key_off[d] = o0[k]; A.d_key_len[d] = o1[k] - o0[k];
-        }
+        const uint32_t j = threadIdx.x + k * 256u, d = T.dofs[fr_engine_of(T, j)] + j;
+        dd[k] = j < cnt && d < n ? d : 0xffffffffu;                  // (d >= n cannot happen: the ranks are a permutation; nothing is accessed out of bounds)
     }
 }
 
+// LDS: two buffers of 1 024 x 8 bytes taken in turn, one column at a time (a barrier per column: a buffer is written again two columns
+// later, behind the barrier of the column between) + FrTile = 16 520 bytes — nine workgroups would fit a CU's 160 KB; the 80 registers
+// (no scratch) leave six of four waves each.  All columns at once (up to 11 x 8 KB) would leave one.
+// Measured under the bench's load (one kernel trace each, same box): 63.4 -> 41.9 us per 1 048 576 requests (profiles/front_runs_ab.txt).
+__global__ __launch_bounds__(256) void k_fr_scatter(FrIn A) {
+    __shared__ FrTile T;
+    __shared__ uint64_t stg[2][FR_TILE];
+    const uint32_t tile = blockIdx.x, tid = threadIdx.x, i0 = tile * FR_TILE + tid;
+    fr_tile_bases(T, A.ctl, A.tile_cnt, A.tile_base, tile);
+    const bool packed = A.ctl->ragged_seq != A.seq;                   // keys of one width: they travel with their requests
+    // packed: request i's key is where the first two offsets say (k_fr_count has compared every request's): no offsets are loaded
+    const uint32_t len0 = fr_len0(A), ko0 = A.key_stride ? 0u : A.key_off[0], kstep = A.key_stride ? A.key_stride : len0;
+    uint32_t p[FR_PER], o0[FR_PER], klen[FR_PER]; uint64_t hits[FR_PER], limit[FR_PER], duration[FR_PER], misc[FR_PER], kw[FR_PER];
+    // where key word w lies in a key of len bytes: whole words, the last one overlapping the one before (nothing is read or written behind
+    // the key, whose neighbour's first bytes are another thread's); a key below 8 bytes is one word of which `len` bytes are stored
+    auto word_at = [](uint32_t w, uint32_t len) { return 8u * w + 8u <= len || len < 8u ? 8u * w : len - 8u; };
+#pragma unroll
+    for (int k = 0; k < FR_PER; ++k) {                               // the loads of the thread's four requests, arrival order: coalesced
+        const uint32_t i = i0 + k * 256u;
+        p[k] = 0xffffffffu; o0[k] = klen[k] = 0; hits[k] = limit[k] = duration[k] = misc[k] = kw[k] = 0;
+        if (i >= A.n) continue;
+        const uint32_t er = A.er[i];
+        if (packed) { o0[k] = ko0 + i * kstep; klen[k] = len0; kw[k] = ld_key_word(A.key_bytes + o0[k]); }   // (a key buffer is readable 8 bytes past its last key)
+        else { o0[k] = fr_key_off(A, i); klen[k] = fr_key_len(A, i, o0[k]); }
+        hits[k] = (uint64_t)A.hits[i]; limit[k] = (uint64_t)A.limit[i]; duration[k] = (uint64_t)A.duration[i];
+        misc[k] = (A.behavior ? A.behavior[i] : 0u) | (uint64_t)(A.algorithm ? A.algorithm[i] : (uint8_t)0) << 32 | (uint64_t)(A.is_owner ? A.is_owner[i] : (uint8_t)0) << 40;
+        const uint32_t e = er >> FR_RANK_BITS;
+        p[k] = T.lbase[e] + (er & ((1u << FR_RANK_BITS) - 1u));
+        const uint32_t d = T.dofs[e] + p[k];
+        A.d_fwd[i] = d < A.n ? d : 0u;                               // (arrival order: the payload stage's k_wire_enc reads it)
+    }
+    uint32_t dd[FR_PER];
+    fr_sorted_places(T, A.n, dd);
+    uint32_t turn = 0;
+    // a column: the thread's four values to their sorted places, a barrier, the thread's four sorted elements back
+    auto through = [&](const uint64_t (&v)[FR_PER], uint64_t (&o)[FR_PER]) {
+        uint64_t* buf = stg[turn++ & 1u];
+#pragma unroll
+        for (int k = 0; k < FR_PER; ++k) if (p[k] < FR_TILE) buf[p[k]] = v[k];
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < FR_PER; ++k) o[k] = dd[k] != 0xffffffffu ? buf[threadIdx.x + k * 256u] : 0ull;
+    };
+    auto column = [&](const uint64_t (&v)[FR_PER], int64_t* dst) {
+        uint64_t o[FR_PER];
+        through(v, o);
+#pragma unroll
+        for (int k = 0; k < FR_PER; ++k) if (dd[k] != 0xffffffffu) dst[dd[k]] = (int64_t)o[k];
+    };
+    // (the optional columns are requested a column ahead of their turn: every load of the kernel at its start would be sixty more registers)
+    uint64_t opt[FR_PER] = {0, 0, 0, 0}, o[FR_PER];
+    auto request = [&](const int64_t* src) {
+#pragma unroll
+        for (int k = 0; k < FR_PER; ++k) if (p[k] != 0xffffffffu) opt[k] = (uint64_t)src[i0 + k * 256u];
+    };
+    column(hits, A.d_hits);
+    column(limit, A.d_limit);
+    if (A.burst) request(A.burst);
+    column(duration, A.d_duration);
+    if (A.burst) column(opt, A.d_burst);
+    if (A.created_at) request(A.created_at);
+    through(misc, o);
+#pragma unroll
+    for (int k = 0; k < FR_PER; ++k) {
+        if (dd[k] == 0xffffffffu) continue;
+        A.d_behavior[dd[k]] = (uint32_t)o[k]; A.d_algorithm[dd[k]] = (uint8_t)(o[k] >> 32);
+        if (A.is_owner) A.d_is_owner[dd[k]] = (uint8_t)(o[k] >> 40);
+    }
+    if (A.created_at) column(opt, A.d_created_at);
+    if (packed) {
+        // the keys as 8-byte words, a word a column: a run's keys are contiguous in d_keys (d x len0), so are the words neighbouring threads store
+        const uint32_t nw = (len0 + 7u) >> 3;
+        for (uint32_t w = 0; w < nw; ++w) {
+            uint64_t next[FR_PER] = {0, 0, 0, 0};
+            if (w + 1 < nw) {                                        // (the next word is on its way while this one goes through LDS)
+#pragma unroll
+                for (int k = 0; k < FR_PER; ++k) if (p[k] != 0xffffffffu) next[k] = ld_key_word(A.key_bytes + o0[k] + word_at(w + 1, len0));
+            }
+            through(kw, o);
+#pragma unroll
+            for (int k = 0; k < FR_PER; ++k) {
+                kw[k] = next[k];
+                if (dd[k] == 0xffffffffu) continue;
+                uint8_t* dst = A.d_keys + (size_t)dd[k] * len0;
+                if (len0 >= 8) __builtin_memcpy(dst + word_at(w, len0), &o[k], 8);
+                else for (uint32_t q = 0; q < len0; ++q) dst[q] = (uint8_t)(o[k] >> (8 * q));
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < FR_PER; ++k) {
+            if (dd[k] == 0xffffffffu) continue;
+            A.d_key_off[dd[k]] = dd[k] * len0;
+            if (dd[k] == A.n - 1) A.d_key_off[A.n] = A.n * len0;
+        }
+    } else {
+        // other keys stay where they are: offset and length travel
+        uint64_t ol[FR_PER];
+#pragma unroll
+        for (int k = 0; k < FR_PER; ++k) ol[k] = o0[k] | (uint64_t)klen[k] << 32;
+        through(ol, o);
+#pragma unroll
+        for (int k = 0; k < FR_PER; ++k) if (dd[k] != 0xffffffffu) { A.d_key_off[dd[k]] = (uint32_t)o[k]; A.d_key_len[dd[k]] = (uint32_t)(o[k] >> 32); }
+    }
+}
+
+// The answers' last hop, mirrored: sorted element j loads its answer from the shares (consecutive threads, consecutive d), arrival
+// position i takes it from LDS at p(i) = lbase[engine] + rank (er[i]: 2 bytes per request instead of fwd's 4) and stores in arrival order.
+// er, tile_cnt, tile_base and ctl->tot are the slot's routing scratch: they are still this generation's here, because the slot is routed
+// into again only behind this kernel — front_route waits for the slot's ev_out, which front_out records behind k_fr_out on every stream
+// but the routing's own (where the stream's order says the same).
+// LDS: the two buffers of k_fr_scatter + status and error as one 16-bit column beside the first = 18 568 bytes, 42 registers, no scratch:
+// eight workgroups per CU (its wave slots).  Under the bench's load 35.1 -> 27.9 us per 1 048 576 requests (profiles/front_runs_ab.txt).
 struct FrOut {
-    uint32_t n; const uint32_t* fwd;
+    uint32_t n; const uint16_t* er; const uint32_t *tile_cnt, *tile_base; const FrontCtl* ctl;
     const uint8_t *d_status, *d_err; const int64_t *d_limit, *d_remaining, *d_reset_time;      // the mirror's answers, in the shares' order
     uint8_t *status, *err; int64_t *limit, *remaining, *reset_time;                           // the caller's result arrays, arrival order
 };
 __global__ __launch_bounds__(256) void k_fr_out(FrOut A) {
-    const uint32_t i0 = blockIdx.x * FR_TILE + threadIdx.x;
-    uint32_t d[FR_PER]; uint8_t st[FR_PER], er[FR_PER]; int64_t l[FR_PER], r[FR_PER], t[FR_PER];
+    __shared__ FrTile T;
+    __shared__ uint64_t stg[2][FR_TILE];
+    __shared__ uint16_t sse[FR_TILE];
+    const uint32_t tile = blockIdx.x, tid = threadIdx.x, i0 = tile * FR_TILE + tid;
+    fr_tile_bases(T, A.ctl, A.tile_cnt, A.tile_base, tile);
+    uint32_t dd[FR_PER], p[FR_PER]; uint16_t se[FR_PER]; int64_t l[FR_PER], r[FR_PER], t[FR_PER];
+    fr_sorted_places(T, A.n, dd);
 #pragma unroll
-    for (int k = 0; k < FR_PER; ++k) d[k] = i0 + k * 256u < A.n ? A.fwd[i0 + k * 256u] : 0xffffffffu;
-#pragma unroll
-    for (int k = 0; k < FR_PER; ++k) {
-        if (d[k] == 0xffffffffu) continue;
-        st[k] = A.d_status[d[k]]; er[k] = A.d_err[d[k]]; l[k] = A.d_limit[d[k]]; r[k] = A.d_remaining[d[k]]; t[k] = A.d_reset_time[d[k]];
+    for (int k = 0; k < FR_PER; ++k) {                               // every load before the first store
+        p[k] = 0xffffffffu;
+        if (i0 + k * 256u < A.n) { const uint32_t er = A.er[i0 + k * 256u]; p[k] = T.lbase[er >> FR_RANK_BITS] + (er & ((1u << FR_RANK_BITS) - 1u)); }
+        if (p[k] >= FR_TILE) p[k] = 0xffffffffu;
+        se[k] = 0; l[k] = r[k] = t[k] = 0;
+        if (dd[k] == 0xffffffffu) continue;
+        se[k] = (uint16_t)(A.d_status[dd[k]] | A.d_err[dd[k]] << 8); l[k] = A.d_limit[dd[k]]; r[k] = A.d_remaining[dd[k]]; t[k] = A.d_reset_time[dd[k]];
     }
 #pragma unroll
+    for (int k = 0; k < FR_PER; ++k) { stg[0][tid + k * 256u] = (uint64_t)l[k]; sse[tid + k * 256u] = se[k]; }
+    __syncthreads();
+#pragma unroll
     for (int k = 0; k < FR_PER; ++k) {
-        if (d[k] == 0xffffffffu) continue;
-        const uint32_t i = i0 + k * 256u;
-        A.limit[i] = l[k]; A.remaining[i] = r[k]; A.reset_time[i] = t[k]; A.status[i] = st[k]; A.err[i] = er[k];
+        if (p[k] == 0xffffffffu) continue;
+        const uint32_t i = i0 + k * 256u; const uint16_t v = sse[p[k]];
+        A.limit[i] = (int64_t)stg[0][p[k]]; A.status[i] = (uint8_t)v; A.err[i] = (uint8_t)(v >> 8);
     }
+#pragma unroll
+    for (int k = 0; k < FR_PER; ++k) stg[1][tid + k * 256u] = (uint64_t)r[k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < FR_PER; ++k) if (p[k] != 0xffffffffu) A.remaining[i0 + k * 256u] = (int64_t)stg[1][p[k]];
+#pragma unroll
+    for (int k = 0; k < FR_PER; ++k) stg[0][tid + k * 256u] = (uint64_t)t[k];      // (everybody has passed the second barrier: nobody reads the first column any more)
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < FR_PER; ++k) if (p[k] != 0xffffffffu) A.reset_time[i0 + k * 256u] = (int64_t)stg[0][p[k]];
 }
 
 }  // namespace guber

@@ -3,7 +3,6 @@
 
 // Host-pointer evaluation: stage -> H2D -> kernels -> D2H.  `idx` (optional) selects a subset of
 // the caller's batch (used to re-submit GUBER_ITEM_E_RETRY items).
-static void item_from_rec(const Rec& s, guber_item_t* out);
 // the same prelude launch_batch has, for the one-launch path
 static int small_prelude(guber_engine* e, const BatchView& B) {
     if (B.now_ms > e->clock_ms) e->clock_ms = B.now_ms;
@@ -95,6 +94,12 @@ static int eval_host_once(guber_engine* e, const guber_batch_t* b, guber_result_
                 if ((++spins & 0x3ff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) { HIPCHK(hipStreamSynchronize(st)); break; }
             }
             if (!sout->fallback) {
+                // a snapshot launched ahead of this batch (small_prelude's maintain, near the cache's size) is older than what is added here:
+                // folded now, not by the maintain() behind the batch — that one would put the counters back to before the batch
+                if (rb_any_armed(e)) {
+                    rb_fold_newest(e);
+                    for (uint32_t i = 0; i < guber_engine::kRb; ++i) if ((int)i != e->rb_ride) e->rb[i].armed = false;   // (launched ahead of this batch: none may be folded behind it)
+                }
                 e->last_ctr.over += sout->over; e->last_ctr.hits += sout->hits; e->last_ctr.misses += sout->misses; e->last_ctr.size += sout->size_delta;
                 done = true;
             } else e->small_fallbacks++;

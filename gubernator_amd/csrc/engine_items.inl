@@ -38,27 +38,7 @@ extern "C" int guber_probe_missing(guber_engine_t* e, const guber_batch_t* b, ui
 }
 
 // ---------------------------------------------------------------------------------------------
-static Rec rec_from_item(const guber_item_t& in) {
-    Rec s; rec_clear(s);
-    s.limit = in.limit; s.duration = in.duration; s.stamp = in.stamp; s.burst = in.burst;
-    s.expire_at = in.expire_at; s.invalid_at = in.invalid_at;
-    if (in.algorithm == GUBER_ALGO_TOKEN_BUCKET) { s.remaining = in.remaining; s.burst = 0; s.meta = make_meta(K_TOKEN, in.status, ALGO_TOKEN); }
-    else if (in.algorithm == GUBER_ALGO_LEAKY_BUCKET) { s.remaining = f2bits(in.remaining_f); s.meta = make_meta(K_LEAKY, 0, ALGO_LEAKY); }
-    else s.meta = make_meta(K_NIL, 0, in.algorithm);   // gubernator.go:435-455: no Value for other algorithms
-    return s;
-}
-static void item_from_rec(const Rec& s, guber_item_t* out) {
-    memset(out, 0, sizeof(*out));
-    out->limit = s.limit; out->duration = s.duration; out->stamp = s.stamp; out->burst = s.burst;
-    out->expire_at = s.expire_at; out->invalid_at = s.invalid_at;
-    if (rec_kind(s) == K_TOKEN) { out->algorithm = GUBER_ALGO_TOKEN_BUCKET; out->status = (uint8_t)rec_status(s); out->remaining = s.remaining; out->burst = 0; }
-    else if (rec_kind(s) == K_LEAKY) { out->algorithm = GUBER_ALGO_LEAKY_BUCKET; out->remaining_f = bits2f(s.remaining); }
-    else {   // CacheItem without a Value: only the CacheItem fields exist
-        out->algorithm = (uint8_t)rec_algo(s);
-        out->limit = out->duration = out->stamp = out->burst = 0;
-    }
-}
-
+// (rec_from_item / item_from_rec: guber_item_conv.h)
 static int add_items_once(guber_engine* e, const guber_item_t* items, const std::vector<uint32_t>& sel, uint8_t* res_out, uint64_t stamp0) {
     const uint32_t n = (uint32_t)sel.size();
     size_t kbytes = 0;

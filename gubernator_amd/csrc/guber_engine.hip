@@ -23,6 +23,7 @@
 #include "guber_test_flags.h"
 #include "guber_kernels.h"
 #include "guber_kernels_lru.h"
+#include "guber_item_conv.h"
 #include <hipcub/hipcub.hpp>
 
 using namespace guber;
@@ -351,6 +352,9 @@ extern "C" int guber_engine_create(const guber_config_t* cfg, guber_engine_t** o
     rc |= e->w_tilemask.ensure((size_t)2 * e->fast_cap * FT_WORDS); rc |= e->w_srec.ensure(e->fast_cap); rc |= e->w_sinv.ensure(e->cap256);
     rc |= e->w_tilerow.ensure((size_t)e->cap256 * FT_MAX_TILES);
     e->force_part = (cfg->flags & GUBER_FLAG_TEST_FORCE_PART) != 0;
+    if (cfg->flags & GUBER_FLAG_TEST_LATE_COUNTERS) {   // (guber_test_flags.h: the counters where production is after seconds to days)
+        e->seq_next = GUBER_TEST_LATE_SEQ_NEXT; e->epoch = GUBER_TEST_LATE_EPOCH; e->fast_epoch16 = GUBER_TEST_LATE_EPOCH16; e->rb_seq = GUBER_TEST_LATE_RB_SEQ;
+    }
     e->use_part = !(cfg->flags & GUBER_FLAG_NO_PART) && !e->force_radix && !e->always_careful;
     // GUBER_PIPELINE: "claims" = never the owner-partitioned pipeline, "part" = also for a batch launched on its own; default: the
     // owner-partitioned pipeline when several tables share the launches (where it is faster: profiles/r04_*), claims otherwise

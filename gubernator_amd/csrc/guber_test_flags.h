@@ -8,3 +8,12 @@
 #define GUBER_FLAG_DIR_CLAIMS 16u       /* accepted and ignored (round-1 tuning knob: per-batch claims in the directory entries) */
 #define GUBER_FLAG_TEST_NO_SMALL 32u    /* batches of <= 256 requests take the two-launch pipeline too (not the one-launch small path) */
 #define GUBER_FLAG_TEST_FORCE_PART 64u  /* every batch (also <= 256 requests, also host-resident ones) takes the owner-partitioned three-launch pipeline */
+#define GUBER_FLAG_TEST_LATE_COUNTERS 256u /* the engine's counters start where production is after seconds to days (the values below): nothing else changes */
+// Where an engine created with GUBER_FLAG_TEST_LATE_COUNTERS starts (guber_engine_create; tests/late_counters.py mirrors the four values and
+// tests/test_late_counters_cpu.py holds the mirror to this file).  The next 4 096 recency stamps have Rec::pad near 0xffffffff and the twenty
+// lower high bits set; stamp 2^52 clears pad, flips every one of those bits and sets bit 52 (Rec::meta bit 31).  A batch takes one epoch and,
+// through the two-launch pipeline, one claim epoch; every counter snapshot takes one ring sequence number.
+#define GUBER_TEST_LATE_SEQ_NEXT ((1ull << 52) - 4096ull) /* guber_engine::seq_next */
+#define GUBER_TEST_LATE_EPOCH (0x7fffffffu - 12u)         /* guber_engine::epoch: the directory's 31-bit epoch (batch_prelude wraps it) */
+#define GUBER_TEST_LATE_EPOCH16 (0xffffu - 12u)           /* guber_engine::fast_epoch16: the claim table's 16-bit epoch (plan_fast wraps it) */
+#define GUBER_TEST_LATE_RB_SEQ (0xffffffffu - 8u)         /* guber_engine::rb_seq: the snapshot ring's sequence (skips 0) */

@@ -80,7 +80,7 @@ typedef struct guber_engine guber_engine_t;
 #define GUBER_FLAG_GLOBAL 8u          /* keep per-bucket pending GLOBAL hits / updates (guber_global_take) */
 #define GUBER_FLAG_NO_PART 128u        /* never take the owner-partitioned pipeline: batches of 257 .. 65 536 requests run the
                                           two-launch pipeline with per-batch claims (round 3's; kept as the retry round) */
-/* (bits 1, 2, 4, 32 and 64 select code paths for the test suite — gubernator_amd/csrc/guber_test_flags.h —, bit 16 is accepted and
+/* (bits 1, 2, 4, 32, 64 and 256 select code paths for the test suite — gubernator_amd/csrc/guber_test_flags.h —, bit 16 is accepted and
  *  ignored: a binding passes none of them) */
 
 /* Engine configuration.  Replaces Config.{CacheSize,Workers,CacheFactory}

@@ -11,7 +11,9 @@
 #define GUBER_KERNELS_PIPELINES_ONLY
 #include "../../gubernator_amd/csrc/guber_kernels.h"
 #include "../../gubernator_amd/csrc/guber_kernels_lru.h"
+#include "../../gubernator_amd/csrc/guber_kernels_ops.h"   // (k_items_probe / k_items_commit / k_item_lookup: ds_add_items, ds_item_lookup)
 #include "../../include/guber_gpu.h"
+#include "../../gubernator_amd/csrc/guber_item_conv.h"
 
 #include "fakehip/fiber_runtime.h"   // the fiber runtime behind fakehip (definitions)
 
@@ -216,6 +218,52 @@ static int ds_eval_piece(DevSim* d, const BatchView& B, const ResultView& R, int
         EvalArgs A{d->T, B, R, W};
         fakehip::launch(dim3(tiles), dim3(256), &A, [&] { k_eval3(A); });
         for (auto v : d->segtiles) if (v) return -2;      // the walk's tile maps must be all zero between batches
+    }
+    return 0;
+}
+// The next recency stamp (guber_engine::seq_next): a test moves it to where production is after seconds, so that the kernel source
+// writes, reads, compares and sorts stamps with bits 32..52 set (tests/test_late_counters_cpu.py); ds_seq reads it back.
+void ds_set_seq(void* h, uint64_t seq) { ((DevSim*)h)->seq_next = seq; }
+uint64_t ds_seq(void* h) { return ((DevSim*)h)->seq_next; }
+// LRUCache.Add (lrucache.go:88-103) of n items with DISTINCT keys as add_items_locked drives it (engine_items.inl): every item carries the
+// stamp of its place in the call, k_items_probe + k_items_commit, then the cache is brought back to its size (evict_to_size: the pre-pass
+// with no requests).  existed[i]: 0 / 1; -> 0, or -4 when an item found no entry.
+int ds_add_items(void* h, const guber_item_t* items, uint32_t n, uint8_t* existed, int64_t now_ms) {
+    DevSim* d = (DevSim*)h;
+    if (n == 0) return 0;
+    std::vector<ItemIn> in(n); std::vector<uint8_t> keys;
+    const uint64_t stamp0 = d->seq_next; d->seq_next += n;
+    for (uint32_t i = 0; i < n; ++i) {
+        const guber_item_t& it = items[i];
+        Rec s = rec_from_item(it);
+        rec_set_stamp(s, stamp0 + i);
+        in[i].rec = s; in[i].key_off = (uint32_t)keys.size(); in[i].key_len = it.key_len;
+        keys.insert(keys.end(), it.key, it.key + it.key_len);
+    }
+    keys.resize(keys.size() + 16, 0);
+    std::vector<uint32_t> slots(n); std::vector<uint8_t> flags(n), res(n);
+    fakehip::launch(dim3((n + 255) / 256), dim3(256), nullptr, [&] { k_items_probe(d->T, in.data(), keys.data(), n, slots.data(), flags.data()); });
+    fakehip::launch(dim3((n + 255) / 256), dim3(256), nullptr, [&] { k_items_commit(d->T, in.data(), keys.data(), n, slots.data(), flags.data(), res.data(), ITEMS_KEEP_STAMP); });
+    for (uint32_t i = 0; i < n; ++i) { if (res[i] > 1) return -4; if (existed) existed[i] = res[i]; }
+    if (d->cache_size && (uint64_t)std::max<long long>(ds_size(d), 0) > d->cache_size) {
+        const uint32_t st = ds_admit(d, LruKeys{}, 0, now_ms);
+        if (st != LRU_NONE && st != LRU_APPLIED) return -3;
+    }
+    return 0;
+}
+// LRUCache.GetItem (mode 0: one stamp, the item moves to the front) / Remove (mode 1) of one key, as item_lookup drives k_item_lookup.
+// *found and, for a found item, its algorithm, status, limit, duration, remaining / remaining_f, stamp, burst and expiry in *out.
+int ds_item_lookup(void* h, const uint8_t* key, uint32_t key_len, int64_t now_ms, int mode, guber_item_t* out, int* found) {
+    DevSim* d = (DevSim*)h;
+    std::vector<uint8_t> kb(key_len + 16, 0);
+    memcpy(kb.data(), key, key_len);
+    Rec s; rec_clear(s);
+    *found = 0;
+    const uint64_t touch = d->seq_next; d->seq_next += 1;
+    fakehip::launch(dim3(1), dim3(64), nullptr, [&] { k_item_lookup(d->T, kb.data(), key_len, now_ms, mode, &s, found, touch); });
+    if (*found && out) {
+        item_from_rec(s, out);
+        out->key_len = key_len;
     }
     return 0;
 }

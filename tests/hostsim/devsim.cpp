@@ -267,6 +267,9 @@ int ds_item_lookup(void* h, const uint8_t* key, uint32_t key_len, int64_t now_ms
     }
     return 0;
 }
+// maintenance between batches for scripts that ask for it (tests/extreme_runs.py "compact"): the rebuild the sim has — one scan of every
+// bucket (k_lru_gather) into a fresh tail list; the table itself stays where it is
+void ds_compact(void* h) { ds_rebuild((DevSim*)h); }
 // `rounds` batches for each of nh (<= EP_MAX) tables — batch r of table j is batches[r * nh + j] — through the owner-partitioned
 // pipeline as a GUBER_FUSE_EP stream enqueues them (guber_engine.hip launch_group): k_part_multi, k_own_multi, then per further round ONE
 // k_evalpart_multi (the previous round's k_eval3 + this round's k_part) and k_own_multi, and the last round's k_eval3_multi.

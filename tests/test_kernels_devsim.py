@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import eval_runs
+import extreme_runs
 import streams
 from support import GREGORIAN, ROOT, GuberBatch, GuberResult, HostBatch, HostResult, Oracle, assert_results_equal, gregorian
 
@@ -569,3 +570,113 @@ def test_the_owner_count_of_a_fused_stream_follows_one_batch_later(lib):
         for r, rnd in enumerate(rounds):
             assert_results_equal(res[r][0], orc.eval(rnd[0]), f"order {order} batch {r}")
         sim.close()
+
+
+# ---- tests/extreme_runs.py: extreme values, InvalidAt items and created_at edges (GPU twin: tests/test_gpu_extreme_runs.py) -----------
+def xr_lib(lib):
+    from gubernator_amd.abi import GuberItem
+    lib.ds_add_items.argtypes = [C.c_void_p, C.POINTER(GuberItem), C.c_uint32, C.POINTER(C.c_uint8), C.c_int64]
+    lib.ds_item_lookup.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_int64, C.c_int, C.POINTER(GuberItem), C.POINTER(C.c_int)]
+    lib.ds_compact.argtypes = [C.c_void_p]
+    return lib
+
+
+class ScriptSim:
+    """tests/extreme_runs.py run_script's backend over a devsim table (ds_add_items / ds_item_lookup as tests/test_late_counters_cpu.py binds them)"""
+
+    def __init__(self, lib, pipeline, slots=1 << 15, max_batch=4096):
+        self.lib, self.sim = xr_lib(lib), Sim(lib, slots=slots, max_batch=max_batch, pipeline=pipeline)
+
+    def add(self, items):
+        from gubernator_amd.abi import GuberItem
+        arr, ex = (GuberItem * len(items))(*items), (C.c_uint8 * len(items))()
+        assert self.lib.ds_add_items(self.sim.h, arr, len(items), ex, 0) == 0
+
+    def eval(self, b):
+        before = self.sim.counters()
+        res = self.sim.eval(b)
+        after = self.sim.counters()
+        assert after[4] == 0, "no request may be answered RETRY"
+        return res, tuple(y - x for x, y in zip(before[:3], after[:3]))
+
+    def get(self, key, now_ms):
+        from gubernator_amd.abi import GuberItem, item_dict
+        out, found = GuberItem(), C.c_int(0)
+        assert self.lib.ds_item_lookup(self.sim.h, key, len(key), now_ms, 0, C.byref(out), C.byref(found)) == 0
+        return item_dict(out, key) if found.value else None
+
+    def compact(self, now_ms):
+        self.lib.ds_compact(self.sim.h)
+
+    def each(self):
+        return None
+
+    def size(self):
+        return self.sim.counters()[3]
+
+    def close(self):
+        self.sim.close()
+
+
+def run_scripts(lib, pipeline, cases):
+    from support import make_item
+    be, orc = ScriptSim(lib, pipeline), Oracle(cache_size=1 << 16)
+    for label, steps in cases:
+        extreme_runs.run_script(f"pipeline {pipeline}: {label}", steps, be, orc, make_item, assert_results_equal)
+    be.close()
+
+
+@pytest.mark.parametrize("pipeline", [1, 0])
+def test_extreme_uniform_runs_through_the_kernel_source(lib, pipeline):
+    """extreme_runs.extreme_uniform_cases: int64 extremes, negatives and pre-loaded float64 Remaining in runs of identical requests, 3-4 hot
+    keys 600 / 257 times each (ranks past a tile: a tile base plus an offset in the group) and in one workgroup's batch, the edges of
+    rank x hits against Remaining = 2^63 - 1, 2^53, 2^53 + 1 by construction — every batch, its counters, the size and GetItem of the hot
+    keys after it equal to the oracle's, through SegRec / GRec / GRecS as the pipelines carry the bucket.  A subset of what
+    tests/test_gpu_extreme_runs.py runs: the 12 edge scripts and the first 30 of its 100 random ones (12 in the builds with a pinned owner count)"""
+    only_where_the_form_matters(lib, pipeline)
+    run_scripts(lib, pipeline, extreme_runs.extreme_uniform_cases(trials=30 if lib.product_form else 12))
+
+
+@pytest.mark.parametrize("pipeline", [1, 0])
+def test_extreme_walked_segments_through_the_kernel_source(lib, pipeline):
+    """extreme_runs.extreme_walk_cases: the same pre-loads under requests that all differ (limit 0 and below, rates that are no integers, an
+    invalid algorithm here and there), and leaky keys whose requests differ in created_at only by fractions of a token: the serial walk.
+    A subset of what tests/test_gpu_extreme_runs.py runs: the first 12 of its 18 random scripts (6 in the builds with a pinned owner count)"""
+    only_where_the_form_matters(lib, pipeline)
+    run_scripts(lib, pipeline, extreme_runs.extreme_walk_cases(trials=12 if lib.product_form else 6))
+
+
+@pytest.mark.parametrize("pipeline", [1, 0])
+def test_invalid_at_items_through_the_kernel_source(lib, pipeline):
+    """extreme_runs.invalid_at_cases: items that carry CacheItem.InvalidAt (W.sinv[] beside the bucket's record) under token runs, leaky
+    runs, a walked segment and the batches at which they expire by that field alone; a survivor reports the invalid_at it was loaded with,
+    after a rebuild too (the scripts name the gets whose item must still carry one)"""
+    only_where_the_form_matters(lib, pipeline)
+    cases = extreme_runs.invalid_at_cases()
+    run_scripts(lib, pipeline, cases if lib.product_form else cases[::3])          # (the other builds run every third script)
+
+
+@pytest.mark.parametrize("pipeline", [1, 0])
+def test_created_at_edge_ranges_through_the_kernel_source(lib, pipeline):
+    """extreme_runs.created_at_edge_cases: created_at ranges on the thresholds of k_part's packed range (-131072 .. 131071 ms from the batch
+    clock, 255 ms wide), inside one tile's group and across the tiles of a key; calendar columns that differ inside one key"""
+    only_where_the_form_matters(lib, pipeline)
+    cases = extreme_runs.created_at_edge_cases(gregorian)
+    run_scripts(lib, pipeline, cases if lib.product_form else cases[::3])
+
+
+def test_invalid_at_items_are_never_answered_by_the_32_byte_record(lib):
+    """k_own: the 32-byte record has no room for InvalidAt.  The steady-state token batch (hits 1, the stored limit and duration) on
+    items with invalid_at 0 is answered by 32-byte records for every (key, tile) group; with invalid_at set on every second key, by none
+    for those keys and still for all the others — and the answers are the oracle's either way"""
+    from support import make_item
+    for invalid_at in (0, extreme_runs.NOW0 + 900_000 + extreme_runs.MINUTE, 2**62, -1):
+        steps, plain_groups, other_groups = extreme_runs.invalid_at_steady_case(invalid_at)
+        be, orc = ScriptSim(lib, 1), Oracle(cache_size=1 << 16)
+        n = [s[1].n for s in steps if s[0] == "eval"][-1]
+        extreme_runs.run_script(f"invalid_at {invalid_at}", steps, be, orc, make_item, assert_results_equal)
+        groups, short_recs, _ = be.sim.part_forms(n)
+        assert groups == plain_groups + other_groups
+        # (-1 has expired: the first batch replaces the item by one without InvalidAt, the second batch meets that one)
+        assert short_recs == (groups if invalid_at in (0, -1) else plain_groups), (invalid_at, groups, short_recs, plain_groups)
+        be.close()

@@ -29,7 +29,7 @@ ABI_SYMBOLS = [
     "guber_pool_create", "guber_pool_destroy", "guber_pool_set_clock", "guber_pool_engine", "guber_pool_batches",
     "guber_pool_get_rate_limits", "guber_compact", "guber_probe_missing", "guber_eval_batch_store",
     "guber_eval_batches_dev", "guber_eval_batches_routed_dev", "guber_front_create", "guber_front_destroy", "guber_front_set_rule", "guber_front_eval_dev",
-               "guber_front_synchronize", "guber_front_stream", "guber_front_stats", "guber_front_latencies", "guber_set_clock", "guber_comm_create_local", "guber_comm_unique_id", "guber_comm_create_rank",
+               "guber_front_synchronize", "guber_front_stream", "guber_front_stats", "guber_front_latencies", "guber_front_probe_missing_dev", "guber_front_eval_store_dev", "guber_front_store_stats", "guber_set_clock", "guber_comm_create_local", "guber_comm_unique_id", "guber_comm_create_rank",
     "guber_comm_destroy", "guber_global_sync", "guber_comm_last_stats", "guber_stage_create", "guber_stage_destroy",
     "guber_stage_batch", "guber_stage_result", "guber_stage_capacity", "guber_stage_submit", "guber_stage_wait", "guber_pool_create_multi",
     "guber_pool_shards", "guber_pool_device_of", "guber_pool_engine_at", "guber_pool_metrics", "guber_pool_set_store", "guber_pool_create_sharded", "guber_pool_shard_of", "guber_pool_load", "guber_pool_store", "guber_global_pending", "guber_global_take_dev", "guber_ring_route_rows_dev", "guber_add_items_dev",
@@ -467,6 +467,14 @@ class FrontStats(C.Structure):
     _fields_ = [("generations", C.c_uint64), ("forced_flushes", C.c_uint64), ("host_waits", C.c_uint64), ("host_wait_us", C.c_uint64)]
 
 
+class FrontAsk(C.Structure):
+    _fields_ = [("index", C.c_void_p), ("engine", C.c_void_p), ("cap", C.c_uint32), ("n", C.c_uint32), ("cut_at", C.c_uint32)]
+
+
+class FrontStoreStats(C.Structure):
+    _fields_ = [("probes", C.c_uint64), ("collisions", C.c_uint64), ("cuts", C.c_uint64), ("asked", C.c_uint64), ("evaluations", C.c_uint64)]
+
+
 class Front:
     """guber_front_t (include/guber_gpu.h): generations of requests in ARRIVAL order, resident in HBM -> routed to the engines on the
     device (XXH64 + the placement's rule: WorkerPool.getWorker, workers.go:180-184) -> evaluated -> answered in ARRIVAL order
@@ -483,6 +491,9 @@ class Front:
         L.guber_front_stats.argtypes = [C.c_void_p, C.POINTER(FrontStats)]
         L.guber_front_stream.argtypes = [C.c_void_p]
         L.guber_front_stream.restype = C.c_void_p
+        L.guber_front_probe_missing_dev.argtypes = [C.c_void_p, C.POINTER(GuberBatch), C.POINTER(FrontAsk)]
+        L.guber_front_eval_store_dev.argtypes = [C.c_void_p, C.POINTER(GuberBatch), C.POINTER(GuberResult), C.POINTER(abi.GuberStoreEvents)]
+        L.guber_front_store_stats.argtypes = [C.c_void_p, C.POINTER(FrontStoreStats)]
         self.engines = list(engines)
         self.placement = placement
         hs = (C.c_void_p * len(self.engines))(*[e.h for e in self.engines])
@@ -498,6 +509,39 @@ class Front:
 
     def synchronize(self):
         _check(lib().guber_front_synchronize(self.h))
+
+    def probe_missing_dev(self, batch_struct, cap=None):
+        """guber_front_probe_missing_dev on a GuberBatch of DEVICE pointers (arrival order): -> (index uint32[], engine uint8[], cut_at).
+        index: the first request of every key that is not resident in the engine it routes to, ascending, among the requests before
+        cut_at; engine: where each was routed (Store.Get's item goes to that engine's add_items).  cap: the ask arrays' size (default:
+        one entry per request, which always suffices); too small raises GuberError(E_NOMEM) whose .needed is the size to come back with."""
+        n = batch_struct.n
+        cap = n if cap is None else cap
+        index, engine = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint8)
+        ask = FrontAsk(index.ctypes.data, engine.ctypes.data, cap, 0, 0)
+        rc = lib().guber_front_probe_missing_dev(self.h, C.byref(batch_struct), C.byref(ask))
+        if rc == E_NOMEM and ask.n > cap:
+            err = GuberError(rc, (lib().guber_last_error() or b"").decode())
+            err.needed = ask.n
+            raise err
+        _check(rc)
+        return index[:ask.n].copy(), engine[:ask.n].copy(), ask.cut_at
+
+    def eval_store_dev(self, batch_struct, result_struct):
+        """guber_front_eval_store_dev: the generation the last probe_missing_dev routed, answers into result_struct's DEVICE arrays
+        (complete on return) -> (flags uint8[n], items GuberItem[n]): GUBER_STORE_* bits and, where ONCHANGE is set, the item right
+        after request i (items[i].key is NULL: the caller owns the keys)."""
+        n = batch_struct.n
+        flags = np.zeros(max(n, 1), np.uint8)
+        items = (GuberItem * max(n, 1))()
+        ev = abi.GuberStoreEvents(flags.ctypes.data, C.cast(items, C.c_void_p))
+        _check(lib().guber_front_eval_store_dev(self.h, C.byref(batch_struct), C.byref(result_struct), C.byref(ev)))
+        return flags[:n], items
+
+    def store_stats(self):
+        st = FrontStoreStats()
+        _check(lib().guber_front_store_stats(self.h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in FrontStoreStats._fields_}
 
     def stream_handle(self):
         return lib().guber_front_stream(self.h)

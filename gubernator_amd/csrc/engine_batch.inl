@@ -148,7 +148,9 @@ static int lru_admit(guber_engine* e, const LruKeys& K, uint32_t n, int64_t now_
     return fail(GUBER_E_HIP, "the eviction pre-pass did not converge");
 }
 
-static int batch_prelude(guber_engine* e, const BatchView& B, Work& W, bool* defer_hard = nullptr) {
+// sf / sa: a front's store generation brings its side channel's place for this batch's requests (GroupItem); otherwise the engine's own
+// (guber_eval_batch_store sets e->W's, null outside store calls)
+static int batch_prelude(guber_engine* e, const BatchView& B, Work& W, bool* defer_hard = nullptr, uint8_t* sf = nullptr, Rec* sa = nullptr) {
     const uint32_t n = B.n;
     if (n > e->max_batch) return fail(GUBER_E_BATCH_TOO_LARGE, "batch larger than guber_config_t.max_batch");
     if (defer_hard && e->epoch + 1 >= 0x7fffffffu) { *defer_hard = true; return 0; }   // (the wrap below enqueues a launch)
@@ -168,6 +170,7 @@ static int batch_prelude(guber_engine* e, const BatchView& B, Work& W, bool* def
         e->epoch = 1;
     }
     W = e->W;
+    if (sf) { W.store_flags = sf; W.store_after = sa; }
     W.epoch = e->epoch;
     W.touch = take_stamps(e, n);
     W.tiles = (n + TILE - 1) / TILE;
@@ -255,10 +258,10 @@ struct PairGroup {
         fsub = F.sub; esub = E.sub; fend = F.end_tile; eend = E.end_tile; fnb = &F.nb; enb = &E.nb; cap = (int)(sizeof(F.sub) / sizeof(F.sub[0]));
         *fnb = *enb = 0;
     }
-    int add(guber_engine* e, const BatchView& B, const ResultView& R, bool host_resident) {
+    int add(guber_engine* e, const BatchView& B, const ResultView& R, bool host_resident, uint8_t* sf = nullptr, Rec* sa = nullptr) {
         if (planned == cap) return fail(GUBER_E_INVALID_ARG, "more tables than the launch's argument block holds");
         Work W; FastPlan P;
-        int rc = batch_prelude(e, B, W);
+        int rc = batch_prelude(e, B, W, nullptr, sf, sa);
         if (!rc) rc = plan_fast(e, B, host_resident, W, P);
         if (rc) return rc;
         tiles += P.ftiles; units += B.n;

@@ -120,7 +120,8 @@ static inline uint64_t dp_now() { return g_dprof ? (uint64_t)std::chrono::durati
 struct DpSpan { int k; uint64_t t0; explicit DpSpan(int kk) : k(kk), t0(dp_now()) {} ~DpSpan() { if (g_dprof) tl_dp[k] += dp_now() - t0; } };
 // (the batches as views: a caller's guber_batch_t, or an engine's share of a front's generation — guber_front.h; hook: the front's
 // "this generation's evaluations on this stream have all been launched" — a held-back evaluation takes it along)
-struct GroupItem { BatchView B; ResultView R; };
+// sf / sa: the Store side channel of a front's store generation (Work::store_flags / store_after for this item's requests), null otherwise
+struct GroupItem { BatchView B; ResultView R; uint8_t* sf = nullptr; Rec* sa = nullptr; };
 static int launch_group(guber_engine* const* grp, const GroupItem* it, int g, uint32_t* enqueued, PendSet* ps = nullptr, EvalHook* hook = nullptr) {
     if (g_dprof) { tl_dp[5]++; tl_dp[6] += (uint64_t)g; }
     // (one batch: launch_batch.  Measured in round 5 and not kept: a sequence of ONE table's batches through these fused launches —
@@ -131,7 +132,9 @@ static int launch_group(guber_engine* const* grp, const GroupItem* it, int g, ui
         EngineLocks locks(1, [&](int) { return e; });
         locks.launch_held_by_others();
         if (e->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
+        if (it[0].sf) { e->W.store_flags = it[0].sf; e->W.store_after = it[0].sa; }   // (launch_batch offsets them for the pieces of a batch it cuts)
         const int rc = launch_batch(e, it[0].B, it[0].R);
+        if (it[0].sf) { e->W.store_flags = nullptr; e->W.store_after = nullptr; }
         if (rc == 0) ++*enqueued;
         return rc;
     }
@@ -184,7 +187,7 @@ static int launch_group(guber_engine* const* grp, const GroupItem* it, int g, ui
     dp_lap(1);
     if (!part) {                                                  // the two-launch pipeline (join is false here: plain preludes, in the group's order)
         PairGroup pg(MF, ME);
-        for (int i = 0; i < g && !rc; ++i) rc = pg.add(grp[i], it[i].B, it[i].R, false);   // (after an error: enqueue what is planned, then report)
+        for (int i = 0; i < g && !rc; ++i) rc = pg.add(grp[i], it[i].B, it[i].R, false, it[i].sf, it[i].sa);   // (after an error: enqueue what is planned, then report)
         dp_lap(2);
         const int rcl = pg.launch(PairGroup::MULTI, true);        // (k_front_multi also for a group that an error cut to one table)
         *enqueued += (uint32_t)pg.planned;
@@ -198,11 +201,11 @@ static int launch_group(guber_engine* const* grp, const GroupItem* it, int g, ui
         const BatchView& B = it[i].B; const ResultView& R = it[i].R;
         Work W; FastPlan P;
         bool defer = false;
-        rc = batch_prelude(e, B, W, join ? &defer : nullptr);
+        rc = batch_prelude(e, B, W, join ? &defer : nullptr, it[i].sf, it[i].sa);
         if (!rc && defer) {                                       // this prelude has something to enqueue or to read: the k_eval3 held back goes first
             join = false;
             rc = flush_pending(*pend, true);
-            if (!rc) rc = batch_prelude(e, B, W);
+            if (!rc) rc = batch_prelude(e, B, W, nullptr, it[i].sf, it[i].sa);
         }
         if (!rc) rc = plan_part(e, B, W, P);
         if (rc) break;                                            // enqueue what is planned, then report
@@ -293,7 +296,7 @@ static int launch_group_mem(guber_engine* const* grp, const GroupItem* it, int g
         if (grp[i]->size_upper + it[i].B.n > grp[i]->cache_size || grp[i]->small_pending) return 1;
     PairGroup pg(HA, DA);
     int rc = 0;
-    for (int i = 0; i < g && !rc; ++i) rc = pg.add(grp[i], it[i].B, it[i].R, false);   // (after an error: enqueue what is planned, then report)
+    for (int i = 0; i < g && !rc; ++i) rc = pg.add(grp[i], it[i].B, it[i].R, false, it[i].sf, it[i].sa);   // (after an error: enqueue what is planned, then report)
     if (pg.planned) {
         if (hipMemcpyAsync(DA, HA, sizeof(MultiArgsMem), hipMemcpyHostToDevice, grp[0]->stream) != hipSuccess) return fail(GUBER_E_HIP, "hipMemcpyAsync");
         const int rcl = pg.launch(PairGroup::MULTI_MEM, true);

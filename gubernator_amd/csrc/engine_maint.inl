@@ -147,7 +147,7 @@ extern "C" int guber_profile_read(guber_engine_t* e, guber_kernel_time_t* out, u
         auto first_stage = [](int k) { return k == KT_FRONT || k == KT_FRONT_MULTI || k == KT_PART || k == KT_PART_MULTI || k == KT_RESOLVE || k == KT_EVALPART_MULTI; };
         // (a front's routing kernels run on a stream of their own and belong to no pass: guber_front_latencies times a generation's way)
         std::vector<const guber_engine::Span*> sp;
-        for (auto& x : e->spans) if (x.kernel < KT_FR_COUNT || x.kernel > KT_FR_OUT) sp.push_back(&x);
+        for (auto& x : e->spans) if (x.kernel < KT_FR_COUNT) sp.push_back(&x);
         size_t g0 = 0;
         for (size_t i = 0; i <= sp.size(); ++i) {
             if (i == sp.size() || (i > g0 && first_stage(sp[i]->kernel))) {

@@ -55,6 +55,18 @@ struct guber_front {
     // start -> the answers' last hop's end (guber_front_latencies)
     struct GenSpan { hipEvent_t a, b; };
     std::vector<GenSpan> gen_spans;
+    // The Store side channel (guber_front_probe_missing_dev / guber_front_eval_store_dev), allocated by the first store call: the election
+    // table and the ask list of guber_kernels_front_store.h, the events in the shares' order (what the evaluation kernels write: cap
+    // bytes + cap x 64) and in arrival order (what k_fr_out_store leaves for the host).
+    struct StoreSide {
+        uint32_t cap = 0, cells = 0;
+        DevBuf<unsigned long long> tag; DevBuf<uint32_t> first, cell, tile_cnt, index; DevBuf<uint8_t> ask, engine, flags, oflags; DevBuf<Rec> after, oafter;
+        DevBuf<FrStoreCtl> ctl; DevBuf<FrStoreTabs> tabs; FrStoreTabs h_tabs{}; FrStoreCtl h_ctl{};
+        std::vector<hipEvent_t> ev;                   // one per engine stream: the routing stream reads the tables behind what is enqueued there
+        bool probed = false, active = false;          // probed: the next slot holds a probed, unevaluated generation; active: guber_front_eval_store_dev is evaluating it
+        uint32_t n = 0, cut_at = 0; const void *key_bytes = nullptr, *key_off = nullptr; int64_t now_ms = 0;
+        uint64_t probes = 0, collisions = 0, cuts = 0, asked = 0, evals = 0;
+    } st;
 };
 
 static size_t front_col(size_t bytes) { return (bytes + 63) & ~(size_t)63; }
@@ -71,6 +83,12 @@ extern "C" void guber_front_destroy(guber_front_t* f) {
         if (s.ev_in) (void)hipEventDestroy(s.ev_in);
         if (s.ev_out) (void)hipEventDestroy(s.ev_out);
         for (auto& h : s.hooks) if (h && h->ev) (void)hipEventDestroy(h->ev);
+    }
+    {
+        auto& t = f->st;
+        t.tag.release(); t.first.release(); t.cell.release(); t.tile_cnt.release(); t.index.release(); t.ask.release(); t.engine.release();
+        t.flags.release(); t.oflags.release(); t.after.release(); t.oafter.release(); t.ctl.release(); t.tabs.release();
+        for (auto ev : t.ev) if (ev) (void)hipEventDestroy(ev);
     }
     f->rt_table.release(); f->rt_exs.release(); f->rt_exh.release();
     if (f->rs2 && f->rs2 != f->rs) (void)hipStreamDestroy(f->rs2);
@@ -209,7 +227,8 @@ static int front_route(guber_front* f, guber_front::Slot& s, const FrontGen* fg,
     const uint32_t tiles = (b->n + FR_TILE - 1u) / FR_TILE;
     guber_engine* e0 = f->eng[0];
     std::unique_lock<std::mutex> pl(e0->mu, std::defer_lock);       // (the per-kernel timing's spans and events belong to the first engine)
-    if (e0->profiling) pl.lock();
+    if (e0->profiling || s.ev_a) pl.lock();
+    if (s.ev_a) e0->event_pool.push_back(s.ev_a);                    // (the slot held a probed generation that was dropped: its span never ended)
     s.ev_a = nullptr;
     if (e0->profiling) { s.ev_a = e0->get_event(); (void)hipEventRecord(s.ev_a, rs); }
     e0->span_begin(KT_FR_COUNT, b->n, rs);
@@ -241,8 +260,12 @@ static int front_out(guber_front* f, guber_front::Slot& s, guber_result_t* r) {
     guber_engine* e0 = f->eng[0];
     std::unique_lock<std::mutex> pl(e0->mu, std::defer_lock);
     if (e0->profiling) pl.lock();
-    e0->span_begin(KT_FR_OUT, s.n, os);
-    if (f->enc_hook) {
+    e0->span_begin(f->st.active ? KT_FR_OUT_STORE : KT_FR_OUT, s.n, os);
+    if (f->st.active) {
+        // a store generation: the events travel home with the answers
+        FrOutStore S{O, f->st.flags.p, f->st.after.p, f->st.oflags.p, f->st.oafter.p};
+        hipLaunchKernelGGL(k_fr_out_store, dim3((s.n + FR_TILE - 1u) / FR_TILE), dim3(256), 0, os, S);
+    } else if (f->enc_hook) {
         // the payload stage (guber_wire_pool.h): the answers' last hop is the encoder — every RPC's GetRateLimitsResp bytes from the shares, through fwd
         guber::WireEnc E = *f->enc_hook;
         E.fwd = s.in.d_fwd; E.d_status = O.d_status; E.d_err = O.d_err; E.d_limit = O.d_limit; E.d_remaining = O.d_remaining; E.d_reset = O.d_reset_time;
@@ -277,6 +300,7 @@ extern "C" int guber_front_eval_dev(guber_front_t* f, const guber_batch_t* gens,
     return front_eval(f, g.data(), results, count, done);
 }
 // `after`: recorded behind the last generation's answers (on the stream their last hop ran on: the answers of a call leave in order)
+static int front_eval_locked(guber_front* f, const FrontGen* gens, guber_result_t* results, uint32_t count, uint32_t* done, hipEvent_t after);
 static int front_eval(guber_front* f, const FrontGen* gens, guber_result_t* results, uint32_t count, uint32_t* done, hipEvent_t after) {
     if (done) *done = 0;
     for (uint32_t k = 0; k < count; ++k) {
@@ -287,6 +311,11 @@ static int front_eval(guber_front* f, const FrontGen* gens, guber_result_t* resu
     }
     std::lock_guard<std::mutex> lk(f->mu);
     if (hipSetDevice(f->device) != hipSuccess) return fail(GUBER_E_HIP, "hipSetDevice");
+    return front_eval_locked(f, gens, results, count, done, after);
+}
+// (f->mu held, the device set, the generations checked; st.active: the one generation is the probed one — guber_front_eval_store_dev)
+static int front_eval_locked(guber_front* f, const FrontGen* gens, guber_result_t* results, uint32_t count, uint32_t* done, hipEvent_t after) {
+    if (f->st.probed && !f->st.active) { f->st.probed = false; f->pre_routed = false; }   // (a probed generation nobody evaluated: dropped, this call routes afresh)
     const uint32_t ne = (uint32_t)f->eng.size(), D = f->depth, ahead = D - 2;
     PendSet pendset;
     bool any_ep = false;
@@ -381,7 +410,8 @@ static int front_eval(guber_front* f, const FrontGen* gens, guber_result_t* resu
                                 b->burst ? A.d_burst + d0 : nullptr, b->created_at ? A.d_created_at + d0 : nullptr,
                                 A.d_algorithm + d0, A.d_behavior + d0, b->is_owner ? A.d_is_owner + d0 : nullptr, nullptr, nullptr, b->now_ms,
                                 0, packed ? nullptr : A.d_key_len + d0};
-                    fifo[j].push_back(GroupItem{B, ResultView{s.o_status + d0, s.o_limit + d0, s.o_remaining + d0, s.o_reset + d0, s.o_err + d0}});
+                    fifo[j].push_back(GroupItem{B, ResultView{s.o_status + d0, s.o_limit + d0, s.o_remaining + d0, s.o_reset + d0, s.o_err + d0},
+                                                f->st.active ? f->st.flags.p + d0 : nullptr, f->st.active ? f->st.after.p + d0 : nullptr});
                 }
                 base += nj;
             }
@@ -438,6 +468,7 @@ static int front_route_ahead(guber_front* f, const FrontGen* g) {
     if (g->b.n > f->cap) return fail(GUBER_E_BATCH_TOO_LARGE, "generation larger than the front was created for");
     if (g->key_stride & 7u) return fail(GUBER_E_INVALID_ARG, "key rows are a multiple of 8 bytes apart");
     std::lock_guard<std::mutex> lk(f->mu);
+    if (f->st.probed) { f->st.probed = false; f->pre_routed = false; }   // (a probed generation nobody evaluated: dropped)
     if (f->pre_routed) return fail(GUBER_E_INVALID_ARG, "guber_front: a generation is routed ahead already");
     if (hipSetDevice(f->device) != hipSuccess) return fail(GUBER_E_HIP, "hipSetDevice");
     const int rc = front_route(f, f->slots[f->generations % f->depth], g, (int64_t)f->generations);
@@ -453,6 +484,211 @@ static bool front_routed_ahead_ready(guber_front* f) {
     for (int q = 0; q <= MULTI_MEM_MAX; ++q)
         if ((uint32_t)(__atomic_load_n((volatile unsigned long long*)&s.host.p->w[q], __ATOMIC_ACQUIRE) >> 32) != s.seq) return false;
     return true;
+}
+
+// ---- the Store side channel of a generation routed on the device (include/guber_gpu.h, Config.Store) -------------------------------
+// guber_front_probe_missing_dev routes the generation into the next slot, the way front_route_ahead leaves one, and runs k_fr_elect /
+// k_fr_missing / k_fr_ask (guber_kernels_front_store.h) behind the routing on its stream; guber_front_eval_store_dev evaluates that
+// generation with the side channel in every share's Work and brings the events home with k_fr_out_store.  Both are synchronous.
+static int front_store_ensure(guber_front* f) {
+    auto& t = f->st;
+    if (t.cap) return 0;
+    const uint32_t cap = std::min<uint32_t>(f->cap, FR_STORE_MAX_N);
+    uint32_t cells = 1024; while (cells < 2 * (uint64_t)cap) cells <<= 1;
+    const size_t tiles = ((size_t)cap + FR_TILE - 1) / FR_TILE;
+    if (t.tag.ensure(cells) || t.first.ensure(2 * (size_t)cells) || t.cell.ensure(cap) || t.tile_cnt.ensure(tiles) || t.index.ensure(cap) || t.ask.ensure(cap) ||
+        t.engine.ensure(cap) || t.flags.ensure(cap) || t.oflags.ensure(cap) || t.after.ensure(cap) || t.oafter.ensure(cap) || t.ctl.ensure(1) || t.tabs.ensure(1)) return GUBER_E_NOMEM;
+    for (size_t q = 0; q < f->streams.size(); ++q) { hipEvent_t ev = nullptr; HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); t.ev.push_back(ev); }
+    t.cells = cells; t.cap = cap;
+    return 0;
+}
+// collision != 0 (two identities in one election cell): cut_at and the ask list from a host copy of the generation's keys and a residency
+// read of every request (k_fr_missing, all = 1).  The engines' locks are the caller's; rs has been synchronised.
+static int front_store_on_host(guber_front* f, guber_front::Slot& s, const FrontGen* g, FrStore E, hipStream_t rs, std::vector<uint32_t>& index, std::vector<uint8_t>& engine, uint32_t* cut_at) {
+    const guber_batch_t& b = g->b;
+    const uint32_t n = b.n;
+    std::vector<uint16_t> er(n); std::vector<uint32_t> off(n + 1, 0), len(n), beh(n, 0); std::vector<uint8_t> miss(n), keys;
+    E.all = 1u;
+    hipLaunchKernelGGL(k_fr_missing, dim3((n + 255u) / 256u), dim3(256), 0, rs, s.in, E);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(miss.data(), E.ask, n, hipMemcpyDeviceToHost, rs));
+    HIPCHK(hipMemcpyAsync(er.data(), s.in.er, (size_t)n * 2, hipMemcpyDeviceToHost, rs));
+    if (b.behavior) HIPCHK(hipMemcpyAsync(beh.data(), b.behavior, (size_t)n * 4, hipMemcpyDeviceToHost, rs));
+    if (g->key_stride) HIPCHK(hipMemcpyAsync(len.data(), g->key_len, (size_t)n * 4, hipMemcpyDeviceToHost, rs));
+    else HIPCHK(hipMemcpyAsync(off.data(), b.key_off, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, rs));
+    HIPCHK(hipStreamSynchronize(rs));
+    size_t base = 0;
+    if (g->key_stride) {
+        keys.resize((size_t)n * g->key_stride);
+        for (uint32_t i = 0; i < n; ++i) off[i] = i * g->key_stride;
+    } else {
+        base = off[0];
+        keys.resize((size_t)off[n] - base);
+        for (uint32_t i = 0; i < n; ++i) len[i] = off[i + 1] - off[i];
+    }
+    if (!keys.empty()) HIPCHK(hipMemcpy(keys.data(), b.key_bytes + base, keys.size(), hipMemcpyDeviceToHost));
+    struct Seen { bool reset; };
+    std::unordered_map<std::string, Seen> seen;
+    seen.reserve(n);
+    uint32_t cut = n;
+    index.clear(); engine.clear();
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint8_t e = (uint8_t)(er[i] >> FR_RANK_BITS);
+        std::string id(1, (char)e);
+        id.append((const char*)keys.data() + (off[i] - base), len[i]);
+        auto ins = seen.emplace(std::move(id), Seen{false});
+        if (!ins.second && ins.first->second.reset) { cut = i; break; }
+        if (ins.second && len[i] != 0 && miss[i]) { index.push_back(i); engine.push_back(e); }
+        if (beh[i] & 8u) ins.first->second.reset = true;
+    }
+    *cut_at = cut;
+    return 0;
+}
+static int front_probe_missing(guber_front* f, const FrontGen* g, guber_front_ask_t* ask) {
+    const guber_batch_t& b = g->b;
+    const uint32_t n = b.n;
+    ask->n = 0; ask->cut_at = n;
+    if (n > FR_STORE_MAX_N) return fail(GUBER_E_BATCH_TOO_LARGE, "a store generation holds at most 1 048 576 requests");
+    if (n > f->cap) return fail(GUBER_E_BATCH_TOO_LARGE, "generation larger than the front was created for");
+    if (b.greg_expire || b.greg_duration) return fail(GUBER_E_INVALID_ARG, "a front takes its calendar intervals from the device");
+    if (g->key_stride & 7u) return fail(GUBER_E_INVALID_ARG, "key rows are a multiple of 8 bytes apart");
+    if (n && (!b.key_bytes || (!g->key_stride && !b.key_off) || !b.hits || !b.limit || !b.duration)) return fail(GUBER_E_INVALID_ARG, "batch is missing a mandatory array");
+    if (ask->cap && (!ask->index || !ask->engine)) return fail(GUBER_E_INVALID_ARG, "null ask arrays");
+    std::lock_guard<std::mutex> lk(f->mu);
+    auto& t = f->st;
+    if (f->pre_routed && !t.probed) return fail(GUBER_E_INVALID_ARG, "guber_front: a generation is routed ahead already");
+    if (hipSetDevice(f->device) != hipSuccess) return fail(GUBER_E_HIP, "hipSetDevice");
+    { const int rc = front_store_ensure(f); if (rc) return rc; }
+    guber_front::Slot& s = f->slots[f->generations % f->depth];
+    guber_engine* e0 = f->eng[0];
+    t.probed = false; f->pre_routed = false;
+    { const int rc = front_route(f, s, g, (int64_t)f->generations); if (rc) return rc; }
+    t.probes++;
+    t.n = n; t.cut_at = n; t.key_bytes = b.key_bytes; t.key_off = g->key_stride ? (const void*)g->key_len : (const void*)b.key_off; t.now_ms = b.now_ms;
+    if (n == 0) { t.probed = true; f->pre_routed = true; return GUBER_OK; }
+    hipStream_t rs = (s.gen & 1) ? f->rs2 : f->rs;
+    uint32_t cells = 1024; while (cells < 2 * (uint64_t)n) cells <<= 1;
+    const uint32_t tiles = (n + FR_TILE - 1u) / FR_TILE;
+    FrStore E{};
+    E.tag = t.tag.p; E.first = t.first.p; E.first_reset = t.first.p + cells; E.cmask = cells - 1u; E.hash_mask = e0->T.hash_mask; E.cell = t.cell.p;
+    E.tabs = t.tabs.p; E.now = b.now_ms; E.ask = t.ask.p; E.ctl = t.ctl.p; E.tile_cnt = t.tile_cnt.p; E.index = t.index.p; E.engine = t.engine.p; E.cap = t.cap; E.all = 0u;
+    std::vector<uint32_t> h_index; std::vector<uint8_t> h_engine;
+    uint32_t n_ask = 0, cut = n;
+    {
+        // the engines' tables as they are now, behind everything enqueued on their streams (evaluations, guber_add_items): read under the
+        // engines' locks, which are kept until the probe has run
+        const int ne = (int)f->eng.size();
+        EngineLocks locks(ne, [&](int i) { return f->eng[i]; });
+        locks.launch_held_by_others();
+        for (int j = 0; j < ne; ++j) t.h_tabs.t[j] = f->eng[j]->T;
+        for (size_t q = 0; q < f->streams.size(); ++q) if (f->streams[q] != rs) { HIPCHK(hipEventRecord(t.ev[q], f->streams[q])); HIPCHK(hipStreamWaitEvent(rs, t.ev[q], 0)); }
+        t.h_ctl = FrStoreCtl{n, 0u, 0u, 0u};
+        HIPCHK(hipMemcpyAsync(t.tabs.p, &t.h_tabs, sizeof(FrStoreTabs), hipMemcpyHostToDevice, rs));
+        HIPCHK(hipMemcpyAsync(t.ctl.p, &t.h_ctl, sizeof(FrStoreCtl), hipMemcpyHostToDevice, rs));
+        HIPCHK(hipMemsetAsync(t.tag.p, 0, (size_t)cells * 8, rs));
+        HIPCHK(hipMemsetAsync(t.first.p, 0xff, (size_t)cells * 8, rs));                 // (first and first_reset)
+        HIPCHK(hipMemsetAsync(t.flags.p, 0, n, rs));                                    // (the side channel's flags: a request answered with an error writes none)
+        e0->span_begin(KT_FR_ELECT, n, rs);
+        hipLaunchKernelGGL(k_fr_elect, dim3((n + 255u) / 256u), dim3(256), 0, rs, s.in, E);
+        e0->span_end();
+        e0->span_begin(KT_FR_MISSING, n, rs);
+        hipLaunchKernelGGL(k_fr_missing, dim3((n + 255u) / 256u), dim3(256), 0, rs, s.in, E);
+        e0->span_end();
+        for (uint32_t w = 0; w < 2; ++w) {
+            e0->span_begin(KT_FR_ASK, n, rs);
+            hipLaunchKernelGGL(k_fr_ask, dim3(tiles), dim3(FR_TILE), 0, rs, E, (const uint16_t*)s.in.er, n, w);
+            e0->span_end();
+        }
+        if (hipGetLastError() != hipSuccess) return fail(GUBER_E_HIP, "kernel launch");
+        HIPCHK(hipMemcpyAsync(&t.h_ctl, t.ctl.p, sizeof(FrStoreCtl), hipMemcpyDeviceToHost, rs));
+        HIPCHK(hipStreamSynchronize(rs));
+        if (t.h_ctl.collision) {
+            t.collisions++;
+            int rc;
+            try { rc = front_store_on_host(f, s, g, E, rs, h_index, h_engine, &cut); }
+            catch (const std::bad_alloc&) { rc = fail(GUBER_E_NOMEM, "guber_front: the host copy of the generation's keys"); }   // (the locks go with the scope)
+            if (rc) return rc;
+            n_ask = (uint32_t)h_index.size();
+        } else { n_ask = t.h_ctl.n_ask; cut = t.h_ctl.cut_at; }
+    }
+    if (cut > n || n_ask > n) return fail(GUBER_E_HIP, "guber_front: the probe left no verdict");
+    ask->n = n_ask; ask->cut_at = cut;
+    t.cut_at = cut;
+    // (cut_at < n: nothing stays routed — the caller comes back with the pieces; otherwise the generation waits in its slot)
+    t.probed = f->pre_routed = cut == n;
+    if (cut < n) t.cuts++;
+    if (n_ask > ask->cap) return fail(GUBER_E_NOMEM, "guber_front: the ask arrays are too small");
+    if (n_ask) {
+        if (t.h_ctl.collision) { memcpy(ask->index, h_index.data(), (size_t)n_ask * 4); memcpy(ask->engine, h_engine.data(), n_ask); }
+        else {
+            HIPCHK(hipMemcpy(ask->index, t.index.p, (size_t)n_ask * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(ask->engine, t.engine.p, n_ask, hipMemcpyDeviceToHost));
+        }
+    }
+    t.asked += n_ask;
+    return GUBER_OK;
+}
+static int front_eval_store(guber_front* f, const FrontGen* g, guber_result_t* result, guber_store_events_t* ev) {
+    const guber_batch_t& b = g->b;
+    const uint32_t n = b.n;
+    if (n && (!ev->flags || !ev->items)) return fail(GUBER_E_INVALID_ARG, "null store event arrays");
+    clear_aggregates(*result);
+    std::lock_guard<std::mutex> lk(f->mu);
+    auto& t = f->st;
+    if (!t.probed || !f->pre_routed || t.cut_at != t.n) return fail(GUBER_E_INVALID_ARG, "guber_front: no probed generation to evaluate (guber_front_probe_missing_dev first; a cut generation goes in pieces)");
+    if (n != t.n || b.key_bytes != t.key_bytes || (g->key_stride ? (const void*)g->key_len : (const void*)b.key_off) != t.key_off || b.now_ms != t.now_ms)
+        return fail(GUBER_E_INVALID_ARG, "guber_front: not the generation the last probe routed");
+    {   // the optional columns the routing scattered are the ones the shares are evaluated with
+        const FrIn& A = f->slots[f->generations % f->depth].in;
+        if (n && ((b.burst != nullptr) != (A.burst != nullptr) || (b.created_at != nullptr) != (A.created_at != nullptr) || (b.is_owner != nullptr) != (A.is_owner != nullptr)))
+            return fail(GUBER_E_INVALID_ARG, "guber_front: burst / created_at / is_owner are not present as they were at the probe");
+    }
+    if (hipSetDevice(f->device) != hipSuccess) return fail(GUBER_E_HIP, "hipSetDevice");
+    t.active = true;
+    uint32_t done = 0;
+    int rc = front_eval_locked(f, g, result, 1, &done, nullptr);
+    t.active = false; t.probed = false;
+    if (rc) return rc;
+    t.evals++;
+    if (n == 0) return GUBER_OK;
+    // the answers and the events are complete on return: every stream the generation ran on
+    for (auto st : f->streams) HIPCHK(hipStreamSynchronize(st));
+    for (hipStream_t st : {f->rs, f->rs2, f->os}) HIPCHK(hipStreamSynchronize(st));
+    std::vector<Rec> after;
+    std::vector<uint32_t> off;
+    try { after.resize(n); off.resize((size_t)n + 1); } catch (...) { return GUBER_E_NOMEM; }
+    HIPCHK(hipMemcpy(ev->flags, t.oflags.p, n, hipMemcpyDeviceToHost));
+    bool any = false;
+    for (uint32_t i = 0; i < n && !any; ++i) any = (ev->flags[i] & GUBER_STORE_ONCHANGE) != 0;
+    if (!any) return GUBER_OK;
+    HIPCHK(hipMemcpy(after.data(), t.oafter.p, (size_t)n * sizeof(Rec), hipMemcpyDeviceToHost));
+    if (g->key_stride) HIPCHK(hipMemcpy(off.data(), g->key_len, (size_t)n * 4, hipMemcpyDeviceToHost));
+    else HIPCHK(hipMemcpy(off.data(), b.key_off, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!(ev->flags[i] & GUBER_STORE_ONCHANGE)) continue;
+        item_from_rec(after[i], &ev->items[i]);
+        ev->items[i].key = nullptr;                                   // (the caller owns the key bytes)
+        ev->items[i].key_len = g->key_stride ? off[i] : off[i + 1] - off[i];
+    }
+    return GUBER_OK;
+}
+extern "C" int guber_front_probe_missing_dev(guber_front_t* f, const guber_batch_t* gen, guber_front_ask_t* ask) {
+    if (!f || !gen || !ask) return fail(GUBER_E_INVALID_ARG, "null argument");
+    FrontGen g; g.b = *gen;
+    return front_probe_missing(f, &g, ask);
+}
+extern "C" int guber_front_eval_store_dev(guber_front_t* f, const guber_batch_t* gen, guber_result_t* result, guber_store_events_t* ev) {
+    if (!f || !ev) return fail(GUBER_E_INVALID_ARG, "null argument");
+    const int rc = check_batch_args(gen, result);
+    if (rc) return rc;
+    FrontGen g; g.b = *gen;
+    return front_eval_store(f, &g, result, ev);
+}
+extern "C" int guber_front_store_stats(guber_front_t* f, guber_front_store_stats_t* out) {
+    if (!f || !out) return fail(GUBER_E_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(f->mu);
+    out->probes = f->st.probes; out->collisions = f->st.collisions; out->cuts = f->st.cuts; out->asked = f->st.asked; out->evaluations = f->st.evals;
+    return GUBER_OK;
 }
 
 extern "C" int guber_front_synchronize(guber_front_t* f) {

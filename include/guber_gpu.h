@@ -367,6 +367,56 @@ typedef struct guber_store_events {
 int guber_probe_missing(guber_engine_t* e, const guber_batch_t* b, uint8_t* missing);
 int guber_eval_batch_store(guber_engine_t* e, const guber_batch_t* b, guber_result_t* r, guber_store_events_t* ev);
 
+/* ---- Config.Store for a front (guber_front_t above): the same two steps for a generation of DEVICE-resident requests in arrival
+ *      order that the front routes over its engines' tables.  Both calls are synchronous (complete on return) and take the front's
+ *      lock like every front call; `gen` and `result` hold DEVICE pointers exactly as for guber_front_eval_dev, `ask` and `ev`
+ *      point to HOST arrays.  A store generation holds at most 1 048 576 requests (GUBER_E_BATCH_TOO_LARGE above that, or above
+ *      the front's max_n).
+ *        1. guber_front_probe_missing_dev routes the generation and reports
+ *             cut_at        the smallest i for which an earlier request q < i has the same key and carries
+ *                           Behavior_RESET_REMAINING (bit 8), whatever its algorithm: the reference asks Store.Get again on the
+ *                           miss that reset causes (algorithms.go:78-90), so request i starts a generation of its own; gen->n
+ *                           when there is none.  (A key's Behavior_GLOBAL requests live in the GLOBAL engine's table when the
+ *                           route rule names one: there they are a key of their own.)
+ *             index[0..n)   ascending: the first request of every key that is not resident (absent or expired at gen->now_ms:
+ *                           what LRUCache.GetItem reports as a miss, lrucache.go:111-128) in the engine it routes to, among the
+ *                           requests [0, cut_at).  Empty keys are never asked for; keys longer than max_key_bytes are.
+ *             engine[k]     the index into the front's engine array where request index[k] was routed: the item Store.Get
+ *                           returns (algorithms.go:45-51, :274-280) goes to guber_add_items(engines[engine[k]], ...), one call
+ *                           per engine touched.
+ *           GUBER_E_NOMEM when cap is too small (ask->n then holds the size needed); n == 0 is legal.
+ *           When cut_at < gen->n nothing stays routed: hand over [0, cut_at) and then the rest as generations of their own (pointer
+ *           arithmetic on the columns).  A second probe replaces what the first routed; any other front call that finds a probed,
+ *           unevaluated generation drops it and routes afresh.
+ *        2. guber_front_eval_store_dev evaluates the generation the last probe routed (n, key_bytes, key_off and now_ms must be
+ *           that generation's, burst / created_at / is_owner present or NULL as they were, and no cut may have been reported:
+ *           GUBER_E_INVALID_ARG otherwise).  result's device arrays hold
+ *           the answers in arrival order; ev->flags[i] / ev->items[i] (HOST, n entries) mean what they mean for
+ *           guber_eval_batch_store, except that items[i].key is NULL (key_len is filled: the caller owns the key bytes).  A request
+ *           answered GUBER_ITEM_E_RETRY has flags[i] = 0.  The host then issues Remove, then OnChange, in arrival order
+ *           (algorithms.go:79-84, :149-153, :252-254).
+ *      Correctness never rests on a hash: two keys of one generation under one 64-bit hash make the probe decide from a host copy
+ *      of the keys (guber_front_store_stats_t.collisions counts those probes).  The documented divergence above (an expired item
+ *      from Store.Get) holds here too, and with caches that bind (live items + requests > cache_size) nothing is claimed beyond
+ *      what the engine-level sequence gives: an item added for a key may be evicted again before its request runs. */
+typedef struct guber_front_ask {
+    uint32_t* index;    /* HOST, cap entries: arrival indices, ascending */
+    uint8_t*  engine;   /* HOST, cap entries: index into the front's engine array */
+    uint32_t  cap;      /* in */
+    uint32_t  n;        /* out */
+    uint32_t  cut_at;   /* out: gen->n when the generation needs no cut */
+} guber_front_ask_t;
+typedef struct guber_front_store_stats {
+    uint64_t probes;        /* guber_front_probe_missing_dev calls that routed a generation */
+    uint64_t collisions;    /* ... of which the host decided from the keys themselves */
+    uint64_t cuts;          /* ... of which reported cut_at < n */
+    uint64_t asked;         /* entries of the ask lists handed out */
+    uint64_t evaluations;   /* guber_front_eval_store_dev calls that evaluated one */
+} guber_front_store_stats_t;
+int guber_front_probe_missing_dev(guber_front_t* f, const guber_batch_t* gen, guber_front_ask_t* ask);
+int guber_front_eval_store_dev(guber_front_t* f, const guber_batch_t* gen, guber_result_t* result, guber_store_events_t* ev);
+int guber_front_store_stats(guber_front_t* f, guber_front_store_stats_t* out);
+
 /* ---- bounded cache: the reference keeps at most CacheSize items in a list ordered by last access (Add and GetItem move an
  *      item to the front, lrucache.go:88-128) and removes the item at the back the moment an insert makes the list longer than
  *      that (:98-100, :138-149) — in the middle of a stream of requests: a key evicted by request i is a new item for request

@@ -229,7 +229,7 @@ int guber_wire_dev_route_ready(guber_wire_dev_t* d, guber_front_t* f);
  *   guber_wire_pool_set_clock         0 = the wall clock (clock.Now(): a stage's items share the instant it was sealed); otherwise a frozen clock
  *                                     in ms, as the reference's tests use clock.Freeze
  *   What this surface does NOT do: the Store's write-through callbacks (store.go:49-65: guber_pool_set_store / guber_eval_batch_store — a daemon
- *   with conf.Store keeps the per-request pool), metadata propagation (RateLimitReq.metadata is skipped), and the decision WHERE a payload goes
+ *   with conf.Store keeps the per-request pool) (the front below it has it: guber_front_eval_store_dev), metadata propagation (RateLimitReq.metadata is skipped), and the decision WHERE a payload goes
  *   (forwarding to the owning peer, gubernator.go:236-283: the Go front end hands over only what this instance evaluates).  Behavior_GLOBAL items
  *   are evaluated on their table and queued for the GLOBAL exchange by the engine as on every other entry point (guber_global_take / _sync);
  *   a rule whose global_engine is set sends them to the device's GLOBAL engine. */

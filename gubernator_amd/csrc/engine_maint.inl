@@ -215,3 +215,4 @@ extern "C" const char* guber_last_error(void) { return g_last_error.c_str(); }
 #include "guber_wire_dev.h"
 #include "guber_wire_pool.h"    // guber_wire_pool_*: the payload stage (caller threads hand over serialized RPCs)
 #include "guber_wire_pool_peer.h"   // guber_wire_pool_update_peer_globals: a broadcast of GLOBAL buckets installed through the pool's rule
+#include "guber_mesh.h"         // guber_mesh_*: a stream that crosses ranks — routed to its owning ranks on the device and answered where it arrived

@@ -1,0 +1,249 @@
+// guber_kernels_mesh.h — the kernels of a mesh of fronts (guber_mesh_*, guber_mesh.h): a rank's generation in ARRIVAL order -> request
+// records grouped by owning rank -> (exchange) -> request columns for the owner's front -> answer records -> (exchange) -> the
+// answers in ARRIVAL order.  Included by guber_kernels.h (and, like the front's kernels, compiled for the host by the tests' fiber emulation).
+#pragma once
+
+namespace guber {
+
+// What the reference does per request between peers — V1Instance.GetRateLimits picks the owner from the ring (gubernator.go:236-283,
+// replicated_hash.go:104-119), forwards what it does not own (GetPeerRateLimits, evaluated there as the owner: gubernator.go:486) and
+// answers in request order (gubernator.proto:51-54) — for a whole generation per rank:
+//   k_mx_count   per request: fnv1 / fnv1a of the key, the ring's point -> destination rank, its rank among the tile's requests of that
+//                destination (stable: arrival order); per tile of 1 024 requests the requests per destination.  GLOBAL requests
+//                (gubernator.go:258-270: never forwarded) and keys the ring cannot place (empty, over-long) have destination self;
+//                own[i] = the is_owner the request is evaluated with
+//   k_mx_scan    k_fr_scan's form: tile bases and the totals per destination, to ctl->tot and — stamped with the call's sequence
+//                number — to pinned memory
+//   k_mx_pack    the tile sorted by destination in LDS (the place is computed: lbase[dest] + rank), one fixed-width record per request
+//                into the send buffer: destination after destination, arrival order inside; consecutive threads write consecutive records
+//   k_mx_unpack  the receiver: records -> request columns (the keys stay in the records: the front takes them as rows)
+//   k_mx_apack   the receiver's answers (its front's result columns, inflow order) -> 32-byte answer records
+//   k_mx_out     k_fr_out's form: the answer of request i lies at the place its request record had in the send buffer (the answers come
+//                back slice by slice in the order the requests left): sorted element j loads record j (coalesced), arrival position i
+//                takes it from LDS at lbase[dest] + rank (er[i]) and stores in arrival order
+// The front's lessons hold (guber_kernels_front.h): no per-workgroup tickets, no system-scope release at a kernel's end, no scratch.
+// (dest[i], place[i]) of a request are er[i] and the tile's bases, as in the front: 2 bytes per request instead of 8.
+//
+// A request record: 64 bytes of columns, then the key row —
+//   +0 key_len (u32; an over-long key travels as max_key + 1 bytes: it only ever earns its item error)  +4 behavior (u32)
+//   +8 hits  +16 limit  +24 duration  +32 burst  +40 created_at  +48 algorithm | is_owner << 8 (u32)  +56 zero
+//   +64 the key, zero-padded to whole 8-byte words (at least four: k_fr_count's speculative hash reads 32 bytes of a row)
+// the layout of the GLOBAL hit rows' columns (guber_global_sync.h); rec_bytes = 64 + (max_key_bytes rounded up to 8, plus 8), rounded
+// up to 64: a record is whole 64-byte sectors.
+constexpr uint32_t MX_COLS = 64;                   // bytes of columns in front of a record's key row
+constexpr uint32_t MX_ANS = 32;                    // an answer record: status | err << 8 (u64), limit, remaining, reset_time
+
+struct MxIn {
+    uint32_t n, self, world, max_key, seq, npts, kind, ring_lds;
+    const uint8_t* key_bytes; const uint32_t* key_off;
+    const int64_t *hits, *limit, *duration, *burst, *created_at; const uint32_t* behavior; const uint8_t* algorithm;
+    int64_t now_ms;
+    const uint64_t* ring_hash; const uint8_t* ring_owner;          // the ring's sorted points (replicated_hash.go:90) and their peers
+    uint16_t* er; uint8_t* own; uint32_t* tile_cnt; uint32_t* tile_base; FrontCtl* ctl; FrontHost* host;
+    uint8_t* send; uint32_t rec_bytes;
+};
+
+// fnv1 / fnv1a (segmentio/fasthash, as replicated_hash.go uses them) over a key of len < 32 bytes held in four words
+__device__ __forceinline__ uint64_t mx_fnv_words4(const uint64_t (&w)[4], uint32_t len, uint32_t kind) {
+    uint64_t h = 0xcbf29ce484222325ULL;
+#pragma unroll
+    for (uint32_t q = 0; q < 4; ++q) {
+        const uint32_t nb = len > 8 * q ? (len - 8 * q < 8 ? len - 8 * q : 8u) : 0u;
+        uint64_t v = w[q];
+        for (uint32_t b = 0; b < nb; ++b, v >>= 8) {
+            if (kind == 1) { h ^= v & 0xffu; h *= 0x100000001b3ULL; } else { h *= 0x100000001b3ULL; h ^= v & 0xffu; }
+        }
+    }
+    return h;
+}
+
+__global__ __launch_bounds__(FR_TILE) void k_mx_count(MxIn A) {
+    GUBER_DYN_LDS(smem);                                             // the ring's hashes (npts x 8 bytes) when they fit beside wtot
+    __shared__ uint32_t wtot[FR_TILE / 64][MULTI_MEM_MAX];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, i = blockIdx.x * FR_TILE + tid;
+    const uint64_t* lh = A.ring_hash;
+    if (A.ring_lds) {
+        uint64_t* l = (uint64_t*)smem;
+        for (uint32_t j = tid; j < A.npts; j += FR_TILE) l[j] = A.ring_hash[j];
+        lh = l;
+    }
+    if (tid < (FR_TILE / 64) * MULTI_MEM_MAX) (&wtot[0][0])[tid] = 0u;
+    __syncthreads();
+    uint32_t e = 0xffu;
+    if (i < A.n) {
+        // keys of one width: the key's words are requested where the first two offsets suggest, together with the request's own offsets,
+        // and used if those confirm the guess (k_fr_count's way: one dependent trip less)
+        const uint32_t o0 = A.key_off[0], len0 = A.key_off[1] - o0, oend = A.key_off[A.n], off_g = o0 + i * len0;
+        uint64_t kw[4] = {0, 0, 0, 0};
+        const bool spec = len0 != 0 && len0 < 32 && (uint64_t)o0 + (uint64_t)i * len0 + 32 <= (uint64_t)oend + 8;   // (a packed buffer is readable 8 bytes past the last key)
+        if (spec) { const uint8_t* kp = A.key_bytes + off_g; kw[0] = ld_key_word(kp); kw[1] = ld_key_word(kp + 8); kw[2] = ld_key_word(kp + 16); kw[3] = ld_key_word(kp + 24); }
+        const uint32_t off = A.key_off[i], len = A.key_off[i + 1] - off;
+        const bool stay = (A.behavior && (A.behavior[i] & 2u)) || len == 0 || len > A.max_key;
+        // ReplicatedConsistentHash.Get (replicated_hash.go:104-119): the first point at or behind the key's hash, wrapping to point 0
+        // (an over-long key is not hashed: nobody looks at the owner of a request that only earns its item error)
+        uint32_t owner = A.self;
+        if (len <= A.max_key) {
+            const uint64_t h = (spec && off == off_g && len == len0) ? mx_fnv_words4(kw, len, A.kind)
+                                                                    : (A.kind == 1 ? fnv1a_64(A.key_bytes + off, len) : fnv1_64(A.key_bytes + off, len));
+            uint32_t lo = 0, hi = A.npts;
+            while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (lh[mid] >= h) hi = mid; else lo = mid + 1; }
+            if (lo == A.npts) lo = 0;
+            owner = A.ring_owner[lo];
+        }
+        e = stay || owner >= A.world ? A.self : owner;
+        A.own[i] = stay ? (uint8_t)(owner == A.self) : (uint8_t)1;   // (forwarded or owned here: evaluated as the owner, gubernator.go:247-256, :486)
+    }
+    // the four-ballot trick of k_fr_count (lanes behind the generation's end carry 0xff and are in nobody's group)
+    unsigned long long same = __ballot(e <= 15u);
+#pragma unroll
+    for (uint32_t b = 0; b < 4; ++b) { const unsigned long long m = __ballot((e >> b) & 1u); same &= ((e >> b) & 1u) ? m : ~m; }
+    if (e > 15u) same = 0ull;
+    uint32_t rank = (uint32_t)__popcll(same & ((1ull << lane) - 1ull));
+    if (same && rank == 0) wtot[wave][e] = (uint32_t)__popcll(same);
+    __syncthreads();
+    if (i < A.n) {
+        for (uint32_t w = 0; w < wave; ++w) rank += wtot[w][e];
+        A.er[i] = (uint16_t)(e << FR_RANK_BITS | rank);
+    }
+    if (tid < MULTI_MEM_MAX) {
+        uint32_t c = 0;
+        for (uint32_t w = 0; w < FR_TILE / 64; ++w) c += wtot[w][tid];
+        A.tile_cnt[blockIdx.x * MULTI_MEM_MAX + tid] = c;
+    }
+}
+
+// k_fr_scan's form — four workgroups, one per four destinations; thread t takes `per` consecutive tiles — without the front's key-width word
+__global__ __launch_bounds__(FR_SCAN_T) void k_mx_scan(MxIn A, uint32_t nt, uint32_t per) {
+    __shared__ uint32_t wsum[FR_SCAN_T / 64][4];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, q = blockIdx.x;
+    const uint32_t t0 = tid * per, t1 = t0 + per < nt ? t0 + per : nt;
+    uint32_t m0 = 0, m1 = 0, m2 = 0, m3 = 0;
+#pragma unroll 1
+    for (uint32_t t = t0; t < t1; ++t) { const uint4 v = ((const uint4*)(A.tile_cnt + (size_t)t * MULTI_MEM_MAX))[q]; m0 += v.x; m1 += v.y; m2 += v.z; m3 += v.w; }
+    const uint32_t i0 = (uint32_t)wave_incl_scan_i32((int)m0), i1 = (uint32_t)wave_incl_scan_i32((int)m1);
+    const uint32_t i2 = (uint32_t)wave_incl_scan_i32((int)m2), i3 = (uint32_t)wave_incl_scan_i32((int)m3);
+    if (lane == 63) { wsum[wave][0] = i0; wsum[wave][1] = i1; wsum[wave][2] = i2; wsum[wave][3] = i3; }
+    __syncthreads();
+    uint32_t e0 = i0 - m0, e1 = i1 - m1, e2 = i2 - m2, e3 = i3 - m3;
+    for (uint32_t w = 0; w < wave; ++w) { e0 += wsum[w][0]; e1 += wsum[w][1]; e2 += wsum[w][2]; e3 += wsum[w][3]; }
+#pragma unroll 1
+    for (uint32_t t = t0; t < t1; ++t) {
+        const uint4 v = ((const uint4*)(A.tile_cnt + (size_t)t * MULTI_MEM_MAX))[q];
+        ((uint4*)(A.tile_base + (size_t)t * MULTI_MEM_MAX))[q] = make_uint4(e0, e1, e2, e3);
+        e0 += v.x; e1 += v.y; e2 += v.z; e3 += v.w;
+    }
+    if (tid < 4) {
+        uint32_t all = 0;
+        for (uint32_t w = 0; w < FR_SCAN_T / 64; ++w) all += wsum[w][tid];
+        A.ctl->tot[4 * q + tid] = all;
+        // (relaxed, system scope: the word carries the call's sequence number, the host needs no fence from the device — FrontHost)
+        __hip_atomic_store(&A.host->w[4 * q + tid], (unsigned long long)A.seq << 32 | all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+// LDS: the tile's requests in the destinations' order (2 KB) + FrTile.  Sorted element j gathers its request's columns (the tile's 1 024
+// requests: lines its neighbours load too) and writes record dofs[dest] + j: consecutive threads, consecutive records, whole sectors.
+__global__ __launch_bounds__(256) void k_mx_pack(MxIn A) {
+    __shared__ FrTile T;
+    __shared__ uint16_t src[FR_TILE];
+    const uint32_t tile = blockIdx.x, tid = threadIdx.x, i0 = tile * FR_TILE + tid;
+    fr_tile_bases(T, A.ctl, A.tile_cnt, A.tile_base, tile);
+#pragma unroll
+    for (int k = 0; k < FR_PER; ++k) {
+        const uint32_t i = i0 + k * 256u;
+        if (i >= A.n) continue;
+        const uint32_t er = A.er[i], p = T.lbase[er >> FR_RANK_BITS] + (er & ((1u << FR_RANK_BITS) - 1u));
+        if (p < FR_TILE) src[p] = (uint16_t)(tid + k * 256u);
+    }
+    __syncthreads();
+    uint32_t dd[FR_PER];
+    fr_sorted_places(T, A.n, dd);
+    const uint32_t area_words = (A.rec_bytes - MX_COLS) >> 3;
+#pragma unroll 1
+    for (int k = 0; k < FR_PER; ++k) {
+        if (dd[k] == 0xffffffffu) continue;
+        const uint32_t i = tile * FR_TILE + src[tid + k * 256u];
+        if (i >= A.n) continue;                                      // (cannot happen: the places are a permutation of the tile's requests)
+        const uint32_t off = A.key_off[i], len = A.key_off[i + 1] - off, lenc = len <= A.max_key ? len : A.max_key + 1u;
+        uint64_t* r = (uint64_t*)(A.send + (size_t)dd[k] * A.rec_bytes);
+        r[0] = lenc | (uint64_t)(A.behavior ? A.behavior[i] : 0u) << 32;
+        r[1] = (uint64_t)A.hits[i]; r[2] = (uint64_t)A.limit[i]; r[3] = (uint64_t)A.duration[i];
+        r[4] = A.burst ? (uint64_t)A.burst[i] : 0ull;
+        r[5] = (uint64_t)(A.created_at ? A.created_at[i] : A.now_ms);           // (gubernator.go:218-220: a request without CreatedAt takes the arrival rank's clock)
+        r[6] = (uint64_t)(A.algorithm ? A.algorithm[i] : (uint8_t)0) | (uint64_t)A.own[i] << 8;
+        r[7] = 0ull;
+        const uint32_t nw = (lenc + 7u) >> 3;
+        uint32_t nwr = nw < 4u ? 4u : nw;
+        if (nwr > area_words) nwr = area_words;
+        const uint8_t* kp = A.key_bytes + off;
+        for (uint32_t w = 0; w < nwr; ++w) {
+            uint64_t v = 0ull;
+            if (w < nw) { v = ld_key_word(kp + 8 * w); if (w == nw - 1) v &= tail_mask(lenc - 8 * w); }   // (nothing is read more than 7 bytes behind the key)
+            r[8 + w] = v;
+        }
+    }
+}
+
+struct MxUnpack {
+    uint32_t m, rec_bytes; const uint8_t* recv;
+    uint32_t* key_len; int64_t *hits, *limit, *duration, *burst, *created_at; uint32_t* behavior; uint8_t *algorithm, *is_owner;
+};
+__global__ __launch_bounds__(256) void k_mx_unpack(MxUnpack U) {
+    const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+    if (q >= U.m) return;
+    const uint4* r = (const uint4*)(U.recv + (size_t)q * U.rec_bytes);
+    const uint4 a = r[0], b = r[1], c = r[2], d = r[3];
+    U.key_len[q] = a.x; U.behavior[q] = a.y;
+    U.hits[q] = (int64_t)((uint64_t)a.z | (uint64_t)a.w << 32);
+    U.limit[q] = (int64_t)((uint64_t)b.x | (uint64_t)b.y << 32); U.duration[q] = (int64_t)((uint64_t)b.z | (uint64_t)b.w << 32);
+    U.burst[q] = (int64_t)((uint64_t)c.x | (uint64_t)c.y << 32); U.created_at[q] = (int64_t)((uint64_t)c.z | (uint64_t)c.w << 32);
+    U.algorithm[q] = (uint8_t)d.x; U.is_owner[q] = (uint8_t)(d.x >> 8);
+}
+
+struct MxAns {
+    uint32_t m; const uint8_t *status, *err; const int64_t *limit, *remaining, *reset_time; uint8_t* out;
+};
+__global__ __launch_bounds__(256) void k_mx_apack(MxAns S) {
+    const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+    if (q >= S.m) return;
+    const uint64_t se = (uint64_t)S.status[q] | (uint64_t)S.err[q] << 8, l = (uint64_t)S.limit[q], rm = (uint64_t)S.remaining[q], t = (uint64_t)S.reset_time[q];
+    uint4* o = (uint4*)(S.out + (size_t)q * MX_ANS);
+    o[0] = make_uint4((uint32_t)se, 0u, (uint32_t)l, (uint32_t)(l >> 32));
+    o[1] = make_uint4((uint32_t)rm, (uint32_t)(rm >> 32), (uint32_t)t, (uint32_t)(t >> 32));
+}
+
+// LDS: the tile's answer records in slice order (32 KB) + FrTile: four workgroups of four waves per CU.
+struct MxOut {
+    uint32_t n; const uint16_t* er; const uint32_t *tile_cnt, *tile_base; const FrontCtl* ctl;
+    const uint8_t* ans;                                              // the answer records as they came back: the send buffer's order
+    uint8_t *status, *err; int64_t *limit, *remaining, *reset_time; // the caller's result arrays, arrival order
+};
+__global__ __launch_bounds__(256) void k_mx_out(MxOut A) {
+    __shared__ FrTile T;
+    __shared__ uint4 stg[FR_TILE][2];
+    const uint32_t tile = blockIdx.x, tid = threadIdx.x, i0 = tile * FR_TILE + tid;
+    fr_tile_bases(T, A.ctl, A.tile_cnt, A.tile_base, tile);
+    uint32_t dd[FR_PER];
+    fr_sorted_places(T, A.n, dd);
+#pragma unroll
+    for (int k = 0; k < FR_PER; ++k) {
+        if (dd[k] == 0xffffffffu) continue;
+        const uint4* a = (const uint4*)(A.ans + (size_t)dd[k] * MX_ANS);
+        stg[tid + k * 256u][0] = a[0]; stg[tid + k * 256u][1] = a[1];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < FR_PER; ++k) {
+        const uint32_t i = i0 + k * 256u;
+        if (i >= A.n) continue;
+        const uint32_t er = A.er[i], p = T.lbase[er >> FR_RANK_BITS] + (er & ((1u << FR_RANK_BITS) - 1u));
+        if (p >= FR_TILE) continue;
+        const uint4 x = stg[p][0], y = stg[p][1];
+        A.status[i] = (uint8_t)x.x; A.err[i] = (uint8_t)(x.x >> 8);
+        A.limit[i] = (int64_t)((uint64_t)x.z | (uint64_t)x.w << 32);
+        A.remaining[i] = (int64_t)((uint64_t)y.x | (uint64_t)y.y << 32);
+        A.reset_time[i] = (int64_t)((uint64_t)y.z | (uint64_t)y.w << 32);
+    }
+}
+
+}  // namespace guber

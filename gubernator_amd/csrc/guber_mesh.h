@@ -1,0 +1,339 @@
+// guber_mesh.h — guber_mesh_*: a mesh of fronts.  Every rank (peer r of a guber_ring_t, one guber_front_t over the engines of one
+// device) hands over the generation that ARRIVED at it; every request is evaluated on the rank the ring names and answered, in arrival
+// order, on the rank where it arrived.  Part of guber_engine.hip's translation unit, behind guber_front.h (it drives the fronts through
+// front_eval) and guber_global_sync.h (whose local transport this one follows).
+//
+// Reference: V1Instance.GetRateLimits (gubernator.go:236-283) picks the owner of a request from the ring (replicated_hash.go:104-119),
+// evaluates what it owns with IsOwner (gubernator.go:247-256), forwards the rest to the owner through GetPeerRateLimits, where it is
+// evaluated as the owner's own (gubernator.go:486), and answers in request order (gubernator.proto:51-54).  Requests with
+// Behavior_GLOBAL are never forwarded (gubernator.go:258-270, 395-421): they stay on the arrival rank with is_owner = (owner == rank)
+// and go to its front's global_engine.  A request the ring cannot place (empty key, key above the rank's max_key_bytes) stays too and
+// earns the front's item error.
+// ORDER.  The reference fans the forwarded items out concurrently (gubernator.go:498) and fixes no order between peers; this one does:
+// per call, owner o evaluates the slices from source 0, 1, ... W-1 — its own in its place in that sequence — each in arrival order.  The
+// requests of one key from one source keep their order; across sources the lower rank goes first.
+//
+// One call:
+//   rank s, its front's routing stream   k_mx_count  k_mx_scan  k_mx_pack                                        [event pack(s)]
+//   host                                 waits for the W x W counts (pinned memory, stamped with the call's number) — nothing else
+//   rank o                               wait pack(s) | copy slice s -> o, s = 0 .. W-1 | k_mx_unpack | the front: the inflow in pieces
+//                                        of at most its max_n (front_eval, count = pieces) | k_mx_apack              [event ans(o)]
+//   rank s                               wait ans(o) | copy answer slice o -> s, o = 0 .. W-1 | k_mx_out          [event done(s)]
+// TRANSPORT.  Two functions, counts and slices (mesh_exchange_counts, mesh_exchange), as gs_exchange_counts / gs_exchange: this is
+// their local mode — every rank in this process, hipMemcpyAsync device-to-device on the RECEIVER's stream, correct for logical ranks
+// that share a GPU as well.  The grouped ncclSend / ncclRecv form and one rank per process belong behind the same two functions and
+// are not built.
+// LOCKS.  The mesh's own mutex for the call; every front's mutex and the engines' (address order, EngineLocks, group by group) are taken
+// where front_eval takes them — the mesh's kernels touch no engine state, and sixteen ranks of sixteen engines are more than one
+// EngineLocks holds.
+#pragma once
+
+struct guber_mesh {
+    std::mutex mu;
+    uint32_t W = 0, max_n = 0, seq = 0, rec_bytes = 0, npts = 0, kind = 0; bool ring_lds = false;
+    struct Rank {
+        guber_front* f = nullptr; int device = 0; hipStream_t st = nullptr;
+        uint32_t max_key = 0, cap_in = 0;                            // cap_in: the largest inflow (W x max_n records)
+        DevBuf<uint8_t> scratch, send, recv, cols, ans_send, ans_recv, ring_o; DevBuf<uint64_t> ring_h; CohBuf<FrontHost> host;
+        MxIn in{}; MxUnpack un{}; MxAns an{};
+        hipEvent_t ev_pack = nullptr, ev_ans = nullptr, ev_done = nullptr; std::vector<hipEvent_t> ev_eng; bool done_recorded = false;
+        uint32_t n = 0;
+    };
+    std::vector<Rank> ranks;
+    guber_mesh_stats_t st{};
+};
+
+extern "C" void guber_mesh_destroy(guber_mesh_t* m) {
+    if (!m) return;
+    for (auto& R : m->ranks) {
+        (void)hipSetDevice(R.device);
+        if (R.st) (void)hipStreamSynchronize(R.st);
+        R.scratch.release(); R.send.release(); R.recv.release(); R.cols.release(); R.ans_send.release(); R.ans_recv.release();
+        R.ring_o.release(); R.ring_h.release(); R.host.release();
+        for (hipEvent_t ev : {R.ev_pack, R.ev_ans, R.ev_done}) if (ev) (void)hipEventDestroy(ev);
+        for (hipEvent_t ev : R.ev_eng) if (ev) (void)hipEventDestroy(ev);
+    }
+    delete m;
+}
+
+extern "C" int guber_mesh_create_local(guber_front_t* const* fronts, uint32_t n_ranks, const guber_ring_t* ring, uint32_t max_n, guber_mesh_t** out) {
+    // (every check before the first HIP call, and before a front is looked into)
+    if (!fronts || !ring || !out) return fail(GUBER_E_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (n_ranks == 0 || n_ranks > (uint32_t)MULTI_MEM_MAX) return fail(GUBER_E_INVALID_ARG, "1 .. 16 ranks per mesh");
+    if (max_n == 0 || max_n > FR_MAX_N) return fail(GUBER_E_BATCH_TOO_LARGE, "a generation holds at most 4 194 304 requests");
+    const uint32_t npts = guber_ring_points(ring, nullptr, nullptr, 0);
+    if (npts == 0 || npts > (1u << 20)) return fail(GUBER_E_INVALID_ARG, "guber_mesh: the ring is empty or has more than 2^20 points");
+    std::vector<uint64_t> hh(npts); std::vector<uint32_t> oo(npts);
+    guber_ring_points(ring, hh.data(), oo.data(), npts);
+    uint32_t peers = 0;
+    for (uint32_t o : oo) peers = std::max(peers, o + 1);
+    if (peers != n_ranks) return fail(GUBER_E_INVALID_ARG, "guber_mesh: rank r is peer r of the ring — the ring has another number of peers");
+    for (uint32_t r = 0; r < n_ranks; ++r) {
+        if (!fronts[r]) return fail(GUBER_E_INVALID_ARG, "null front");
+        for (uint32_t q = 0; q < r; ++q) if (fronts[q] == fronts[r]) return fail(GUBER_E_INVALID_ARG, "a front twice in one mesh");
+    }
+    std::unique_ptr<guber_mesh, void (*)(guber_mesh*)> m(new guber_mesh(), [](guber_mesh* p) { guber_mesh_destroy(p); });
+    m->W = n_ranks; m->max_n = max_n; m->npts = npts; m->kind = (uint32_t)guber_ring_kind(ring);
+    // the ring's hashes in LDS while they fit beside k_mx_count's 1 KB in the 64 KB every launch may take (fifteen peers of 512
+    // replicas do); a larger ring is searched where it lies — 64 KB that stay in the L2
+    m->ring_lds = (size_t)npts * 8 + 2048 <= 64 * 1024;
+    uint32_t max_key = 0;
+    for (uint32_t r = 0; r < n_ranks; ++r) max_key = std::max(max_key, fronts[r]->max_key);
+    m->rec_bytes = (MX_COLS + ((max_key + 7u) & ~7u) + 8u + 63u) & ~63u;
+    std::vector<uint8_t> o8(npts);
+    for (uint32_t j = 0; j < npts; ++j) o8[j] = (uint8_t)oo[j];
+    m->ranks.resize(n_ranks);
+    const size_t tiles = ((size_t)max_n + FR_TILE - 1) / FR_TILE, cap_in = (size_t)n_ranks * max_n, rb = m->rec_bytes;
+    for (uint32_t r = 0; r < n_ranks; ++r) {
+        auto& R = m->ranks[r];
+        guber_front* f = fronts[r];
+        R.f = f; R.device = f->device; R.st = f->rs; R.max_key = f->max_key; R.cap_in = (uint32_t)std::min<size_t>(cap_in, 0xffffffffu);
+        // (the front addresses a piece's key rows with 32-bit offsets)
+        if ((uint64_t)std::min<size_t>(f->cap, cap_in) * rb > 0xffffffffull) return fail(GUBER_E_BATCH_TOO_LARGE, "guber_mesh: a front's generation of key rows exceeds 4 GB");
+        if (n_ranks == 1) continue;                                  // (one rank: the front alone, no exchange)
+        if (hipSetDevice(R.device) != hipSuccess) return fail(GUBER_E_HIP, "hipSetDevice");
+        const size_t scratch = front_col((size_t)max_n * 2) + front_col(max_n) + 2 * front_col(tiles * MULTI_MEM_MAX * 4) + front_col(sizeof(FrontCtl));
+        const size_t cols = 5 * front_col(cap_in * 8) + 2 * front_col(cap_in * 4) + 2 * front_col(cap_in) +      // the inflow's request columns
+                            3 * front_col(cap_in * 8) + 2 * front_col(cap_in);                                 // its answers
+        if (R.scratch.ensure(scratch) || R.send.ensure((size_t)max_n * rb + 64) || R.recv.ensure(cap_in * rb + 64) || R.cols.ensure(cols) ||
+            R.ans_send.ensure(cap_in * MX_ANS + 64) || R.ans_recv.ensure((size_t)max_n * MX_ANS + 64) || R.ring_h.ensure(npts) || R.ring_o.ensure(npts) ||
+            R.host.ensure(1)) return GUBER_E_NOMEM;
+        memset((void*)R.host.p, 0, sizeof(FrontHost));
+        MxIn& A = R.in;
+        uint8_t* p = R.scratch.p;
+        A.er = (uint16_t*)p; p += front_col((size_t)max_n * 2); A.own = p; p += front_col(max_n);
+        A.tile_cnt = (uint32_t*)p; p += front_col(tiles * MULTI_MEM_MAX * 4); A.tile_base = (uint32_t*)p; p += front_col(tiles * MULTI_MEM_MAX * 4);
+        A.ctl = (FrontCtl*)p;
+        A.host = R.host.p; A.send = R.send.p; A.rec_bytes = m->rec_bytes;
+        A.self = r; A.world = n_ranks; A.max_key = R.max_key; A.npts = npts; A.kind = m->kind; A.ring_lds = m->ring_lds ? 1u : 0u;
+        A.ring_hash = R.ring_h.p; A.ring_owner = R.ring_o.p;
+        p = R.cols.p;
+        MxUnpack& U = R.un;
+        U.rec_bytes = m->rec_bytes; U.recv = R.recv.p;
+        U.hits = (int64_t*)p; p += front_col(cap_in * 8); U.limit = (int64_t*)p; p += front_col(cap_in * 8); U.duration = (int64_t*)p; p += front_col(cap_in * 8);
+        U.burst = (int64_t*)p; p += front_col(cap_in * 8); U.created_at = (int64_t*)p; p += front_col(cap_in * 8);
+        U.key_len = (uint32_t*)p; p += front_col(cap_in * 4); U.behavior = (uint32_t*)p; p += front_col(cap_in * 4);
+        U.algorithm = p; p += front_col(cap_in); U.is_owner = p; p += front_col(cap_in);
+        MxAns& S = R.an;
+        int64_t* a_limit = (int64_t*)p; p += front_col(cap_in * 8); int64_t* a_rem = (int64_t*)p; p += front_col(cap_in * 8); int64_t* a_reset = (int64_t*)p; p += front_col(cap_in * 8);
+        uint8_t* a_status = p; p += front_col(cap_in); uint8_t* a_err = p; p += front_col(cap_in);
+        S.status = a_status; S.err = a_err; S.limit = a_limit; S.remaining = a_rem; S.reset_time = a_reset; S.out = R.ans_send.p;
+        HIPCHK(hipMemcpyAsync(R.ring_h.p, hh.data(), (size_t)npts * 8, hipMemcpyHostToDevice, R.st));
+        HIPCHK(hipMemcpyAsync(R.ring_o.p, o8.data(), npts, hipMemcpyHostToDevice, R.st));
+        HIPCHK(hipMemsetAsync(A.ctl, 0, sizeof(FrontCtl), R.st));
+        HIPCHK(hipMemsetAsync(R.recv.p, 0, cap_in * rb + 64, R.st));      // (key rows are read as 8-byte words: every byte of a row is defined)
+        HIPCHK(hipEventCreateWithFlags(&R.ev_pack, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&R.ev_ans, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&R.ev_done, hipEventDisableTiming));
+        for (size_t q = 0; q < f->streams.size() + 1; ++q) { hipEvent_t ev = nullptr; HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); R.ev_eng.push_back(ev); }
+        HIPCHK(hipStreamSynchronize(R.st));
+    }
+    *out = m.release();
+    return GUBER_OK;
+}
+
+// table[s * W + o] = requests rank s sends rank o: the host waits for every sender's k_mx_scan words of THIS call — the only wait of a call
+static int mesh_exchange_counts(guber_mesh* m, std::vector<uint32_t>& table) {
+    const uint32_t W = m->W;
+    table.assign((size_t)W * W, 0);
+    for (uint32_t s = 0; s < W; ++s) {
+        auto& R = m->ranks[s];
+        if (R.n == 0) continue;
+        auto reported = [&]() {
+            for (uint32_t q = 0; q < (uint32_t)MULTI_MEM_MAX; ++q)
+                if ((uint32_t)(__atomic_load_n((volatile unsigned long long*)&R.host.p->w[q], __ATOMIC_ACQUIRE) >> 32) != m->seq) return false;
+            return true;
+        };
+        uint32_t spins = 0;
+        while (!reported()) {
+            if (++spins > 2000) {
+                std::this_thread::yield();
+                if ((spins & 0x3ffu) == 0) {
+                    if (hipSetDevice(R.device) != hipSuccess) return fail(GUBER_E_HIP, "hipSetDevice");
+                    if (hipStreamQuery(R.st) != hipErrorNotReady && !reported()) return fail(GUBER_E_HIP, "guber_mesh: the routing of a generation did not report");
+                }
+            }
+        }
+        uint64_t tot = 0;
+        for (uint32_t o = 0; o < (uint32_t)MULTI_MEM_MAX; ++o) {
+            const uint32_t c = (uint32_t)R.host.p->w[o];
+            if (o < W) table[(size_t)s * W + o] = c;
+            tot += c;
+        }
+        if (tot != R.n) return fail(GUBER_E_HIP, "guber_mesh: the slices do not add up to the generation");
+    }
+    return 0;
+}
+// rank `to` receives from every rank the slice meant for it, in rank order, on ITS stream behind the sender's event: request records
+// (answers = false: sender s's slice for `to` lies behind its slices for the ranks below `to`) or answer records (answers = true: owner
+// o's answers for `to` lie behind its answers for the sources below `to` — the transpose)
+static int mesh_exchange(guber_mesh* m, const std::vector<uint32_t>& table, uint32_t to, bool answers) {
+    const uint32_t W = m->W;
+    auto& R = m->ranks[to];
+    const size_t rb = answers ? MX_ANS : m->rec_bytes;
+    uint8_t* dst = answers ? R.ans_recv.p : R.recv.p;
+    size_t roff = 0;
+    for (uint32_t p = 0; p < W; ++p) {
+        auto& P = m->ranks[p];
+        const size_t cnt = answers ? table[(size_t)to * W + p] : table[(size_t)p * W + to];
+        if (!cnt) continue;
+        size_t soff = 0;
+        for (uint32_t q = 0; q < to; ++q) soff += answers ? table[(size_t)q * W + p] : table[(size_t)p * W + q];
+        if (p != to) HIPCHK(hipStreamWaitEvent(R.st, answers ? P.ev_ans : P.ev_pack, 0));
+        HIPCHK(hipMemcpyAsync(dst + roff * rb, (answers ? P.ans_send.p : P.send.p) + soff * rb, cnt * rb, hipMemcpyDeviceToDevice, R.st));
+        if (p != to) { m->st.forwarded += answers ? 0 : cnt; m->st.bytes_moved += cnt * rb; }
+        roff += cnt;
+    }
+    return 0;
+}
+
+// generation b in pieces of at most the front's max_n, through the count argument of front_eval
+static int mesh_front_pieces(guber_mesh* m, guber_front* f, const FrontGen& g, const guber_result_t& r) {
+    std::vector<FrontGen> gens; std::vector<guber_result_t> res;
+    const uint32_t n = g.b.n, step = f->cap;
+    for (uint32_t pos = 0; pos < n; pos += step) {
+        FrontGen p = g;
+        p.b.n = std::min(step, n - pos);
+        if (g.key_stride) { p.b.key_bytes = g.b.key_bytes + (size_t)pos * g.key_stride; p.key_len = g.key_len + pos; }
+        else p.b.key_off = g.b.key_off + pos;
+        p.b.hits += pos; p.b.limit += pos; p.b.duration += pos;
+        if (p.b.burst) p.b.burst += pos;
+        if (p.b.created_at) p.b.created_at += pos;
+        if (p.b.behavior) p.b.behavior += pos;
+        if (p.b.algorithm) p.b.algorithm += pos;
+        if (p.b.is_owner) p.b.is_owner += pos;
+        guber_result_t q{};
+        q.status = r.status + pos; q.err = r.err + pos; q.limit = r.limit + pos; q.remaining = r.remaining + pos; q.reset_time = r.reset_time + pos;
+        gens.push_back(p); res.push_back(q);
+    }
+    m->st.inflow_pieces += gens.size();
+    uint32_t done = 0;
+    return front_eval(f, gens.data(), res.data(), (uint32_t)gens.size(), &done);
+}
+
+static int mesh_eval(guber_mesh* m, const guber_batch_t* gens, guber_result_t* results) {
+    const uint32_t W = m->W;
+    uint64_t total = 0;
+    for (uint32_t r = 0; r < W; ++r) { m->ranks[r].n = gens[r].n; total += gens[r].n; clear_aggregates(results[r]); }
+    m->st.calls++; m->st.requests += total;
+    if (W == 1) {
+        if (gens[0].n == 0) return 0;
+        FrontGen g; g.b = gens[0];
+        return mesh_front_pieces(m, m->ranks[0].f, g, results[0]);
+    }
+    if (++m->seq == 0) m->seq = 1;
+    // routing: count, scan, pack on every rank's stream
+    for (uint32_t r = 0; r < W; ++r) {
+        auto& R = m->ranks[r];
+        HIPCHK(hipSetDevice(R.device));
+        // (the last call's copies on the other ranks' streams have read what this call writes: its request and answer records)
+        for (uint32_t q = 0; q < W; ++q) if (q != r && m->ranks[q].done_recorded) HIPCHK(hipStreamWaitEvent(R.st, m->ranks[q].ev_done, 0));
+        const guber_batch_t& b = gens[r];
+        if (b.n) {
+            MxIn& A = R.in;
+            A.n = b.n; A.seq = m->seq; A.now_ms = b.now_ms;
+            A.key_bytes = b.key_bytes; A.key_off = b.key_off; A.hits = b.hits; A.limit = b.limit; A.duration = b.duration; A.burst = b.burst;
+            A.created_at = b.created_at; A.behavior = b.behavior; A.algorithm = b.algorithm;
+            const uint32_t tiles = (b.n + FR_TILE - 1u) / FR_TILE;
+            hipLaunchKernelGGL(k_mx_count, dim3(tiles), dim3(FR_TILE), m->ring_lds ? (size_t)m->npts * 8 : 0, R.st, A);
+            hipLaunchKernelGGL(k_mx_scan, dim3(MULTI_MEM_MAX / 4), dim3(FR_SCAN_T), 0, R.st, A, tiles, (tiles + FR_SCAN_T - 1) / FR_SCAN_T);
+            hipLaunchKernelGGL(k_mx_pack, dim3(tiles), dim3(256), 0, R.st, A);
+            if (hipGetLastError() != hipSuccess) return fail(GUBER_E_HIP, "kernel launch");
+        }
+        HIPCHK(hipEventRecord(R.ev_pack, R.st));
+    }
+    std::vector<uint32_t> table;
+    { const int rc = mesh_exchange_counts(m, table); if (rc) return rc; }
+    // every owner: its inflow, its front, its answers as records
+    int rc = 0;
+    for (uint32_t o = 0; o < W; ++o) {
+        auto& R = m->ranks[o];
+        guber_front* f = R.f;
+        HIPCHK(hipSetDevice(R.device));
+        uint64_t inflow = 0;
+        for (uint32_t s = 0; s < W; ++s) inflow += table[(size_t)s * W + o];
+        if (inflow > R.cap_in) return fail(GUBER_E_HIP, "guber_mesh: an inflow larger than every rank's generation together");
+        if (inflow) {
+            { const int r2 = mesh_exchange(m, table, o, false); if (r2) return r2; }
+            MxUnpack U = R.un; U.m = (uint32_t)inflow;
+            hipLaunchKernelGGL(k_mx_unpack, dim3((U.m + 255u) / 256u), dim3(256), 0, R.st, U);
+            if (hipGetLastError() != hipSuccess) return fail(GUBER_E_HIP, "kernel launch");
+            if (f->rs != R.st || f->rs2 != R.st) {                   // (the front routes on a stream that is not the one the mesh was created on)
+                HIPCHK(hipEventRecord(R.ev_eng.back(), R.st));
+                for (hipStream_t st : {f->rs, f->rs2}) if (st != R.st) HIPCHK(hipStreamWaitEvent(st, R.ev_eng.back(), 0));
+            }
+            FrontGen g;
+            g.b = guber_batch_t{};
+            g.b.n = U.m; g.b.key_bytes = R.recv.p + MX_COLS; g.b.hits = U.hits; g.b.limit = U.limit; g.b.duration = U.duration; g.b.burst = U.burst;
+            g.b.created_at = U.created_at; g.b.algorithm = U.algorithm; g.b.behavior = U.behavior; g.b.is_owner = U.is_owner; g.b.now_ms = gens[0].now_ms;
+            g.key_stride = m->rec_bytes; g.key_len = U.key_len;
+            guber_result_t ar{};
+            ar.status = (uint8_t*)R.an.status; ar.err = (uint8_t*)R.an.err; ar.limit = (int64_t*)R.an.limit; ar.remaining = (int64_t*)R.an.remaining; ar.reset_time = (int64_t*)R.an.reset_time;
+            rc = mesh_front_pieces(m, f, g, ar);
+            if (rc) return rc;
+            // the answers' records behind everything the front has enqueued: its engines' streams and its own
+            HIPCHK(hipSetDevice(R.device));
+            size_t q = 0;
+            for (hipStream_t st : f->streams) if (st != R.st) { HIPCHK(hipEventRecord(R.ev_eng[q], st)); HIPCHK(hipStreamWaitEvent(R.st, R.ev_eng[q], 0)); ++q; }
+            for (hipStream_t st : {f->rs, f->rs2, f->os}) if (st && st != R.st) { HIPCHK(hipEventRecord(R.ev_eng.back(), st)); HIPCHK(hipStreamWaitEvent(R.st, R.ev_eng.back(), 0)); }
+            MxAns S = R.an; S.m = U.m;
+            hipLaunchKernelGGL(k_mx_apack, dim3((S.m + 255u) / 256u), dim3(256), 0, R.st, S);
+            if (hipGetLastError() != hipSuccess) return fail(GUBER_E_HIP, "kernel launch");
+        }
+        HIPCHK(hipEventRecord(R.ev_ans, R.st));
+    }
+    // every source: its answers home, in arrival order
+    for (uint32_t s = 0; s < W; ++s) {
+        auto& R = m->ranks[s];
+        HIPCHK(hipSetDevice(R.device));
+        if (R.n) {
+            { const int r2 = mesh_exchange(m, table, s, true); if (r2) return r2; }
+            MxOut O{};
+            O.n = R.n; O.er = R.in.er; O.tile_cnt = R.in.tile_cnt; O.tile_base = R.in.tile_base; O.ctl = R.in.ctl; O.ans = R.ans_recv.p;
+            O.status = results[s].status; O.err = results[s].err; O.limit = results[s].limit; O.remaining = results[s].remaining; O.reset_time = results[s].reset_time;
+            hipLaunchKernelGGL(k_mx_out, dim3((R.n + FR_TILE - 1u) / FR_TILE), dim3(256), 0, R.st, O);
+            if (hipGetLastError() != hipSuccess) return fail(GUBER_E_HIP, "kernel launch");
+        }
+        HIPCHK(hipEventRecord(R.ev_done, R.st));
+        R.done_recorded = true;
+    }
+    return 0;
+}
+
+// gens[r] -> results[r], r = 0 .. n_ranks-1: DEVICE pointers on rank r's device, requests and answers in arrival order.  Asynchronous like
+// guber_front_eval_dev: returns when the answers' last hop is enqueued (guber_mesh_synchronize waits).
+extern "C" int guber_mesh_eval_dev(guber_mesh_t* m, const guber_batch_t* gens, guber_result_t* results) {
+    if (!m || !gens || !results) return fail(GUBER_E_INVALID_ARG, "null argument");
+    for (uint32_t r = 0; r < m->W; ++r) {
+        const int rc = check_batch_args(&gens[r], &results[r]);
+        if (rc) return rc;
+        if (gens[r].n > m->max_n) return fail(GUBER_E_BATCH_TOO_LARGE, "generation larger than the mesh was created for");
+        if (gens[r].now_ms != gens[0].now_ms) return fail(GUBER_E_INVALID_ARG, "guber_mesh: the generations of a call carry one now_ms");
+        if (gens[r].is_owner) return fail(GUBER_E_INVALID_ARG, "guber_mesh: the ring decides ownership (is_owner must be NULL)");
+        if (gens[r].greg_expire || gens[r].greg_duration) return fail(GUBER_E_INVALID_ARG, "a front takes its calendar intervals from the device");
+    }
+    std::lock_guard<std::mutex> lk(m->mu);
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = mesh_eval(m, gens, results);
+    m->st.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
+}
+
+extern "C" int guber_mesh_synchronize(guber_mesh_t* m) {
+    if (!m) return fail(GUBER_E_INVALID_ARG, "null mesh");
+    std::lock_guard<std::mutex> lk(m->mu);
+    for (auto& R : m->ranks) {
+        const int rc = guber_front_synchronize(R.f);
+        if (rc) return rc;
+        HIPCHK(hipStreamSynchronize(R.st));                          // (the answers' last hop: the stream the mesh was created on)
+    }
+    return GUBER_OK;
+}
+
+extern "C" int guber_mesh_stats(guber_mesh_t* m, guber_mesh_stats_t* out) {
+    if (!m || !out) return fail(GUBER_E_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    *out = m->st;
+    return GUBER_OK;
+}

@@ -1,0 +1,68 @@
+"""ctypes binding of the mesh of fronts (include/guber_gpu.h: guber_mesh_*; implementation gubernator_amd/csrc/guber_mesh.h,
+kernels guber_kernels_mesh.h): rank r is peer r of a Ring and owns one Front; a call takes the generation that arrived at every
+rank, evaluates every request on the rank the ring names (gubernator.go:236-283) and answers it, in arrival order, where it arrived."""
+import ctypes as C
+
+from . import GuberBatch, GuberError, GuberResult, lib
+
+
+class MeshStats(C.Structure):
+    _fields_ = [("calls", C.c_uint64), ("requests", C.c_uint64), ("forwarded", C.c_uint64), ("bytes_moved", C.c_uint64),
+                ("inflow_pieces", C.c_uint64), ("ms", C.c_double)]
+
+
+_bound = False
+
+
+def _lib():
+    global _bound
+    L = lib()
+    if not _bound:
+        L.guber_mesh_create_local.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.guber_mesh_eval_dev.argtypes = [C.c_void_p, C.POINTER(GuberBatch), C.POINTER(GuberResult)]
+        L.guber_mesh_synchronize.argtypes = [C.c_void_p]
+        L.guber_mesh_stats.argtypes = [C.c_void_p, C.POINTER(MeshStats)]
+        L.guber_mesh_destroy.argtypes = [C.c_void_p]
+        L.guber_mesh_destroy.restype = None
+        _bound = True
+    return L
+
+
+def _check(rc):
+    if rc != 0:
+        L = lib()
+        raise GuberError(rc, f"{L.guber_strerror(rc).decode()} ({L.guber_last_error().decode()})")
+
+
+class Mesh:
+    """guber_mesh_t over fronts[r] = rank r = peer r of `ring`; max_n: the largest generation per rank and call.  Every rank lives in
+    this process (guber_mesh_create_local); the ranks' fronts may share a device."""
+
+    def __init__(self, fronts, ring, max_n):
+        self.fronts, self.ring = list(fronts), ring
+        arr = (C.c_void_p * max(len(self.fronts), 1))(*[f.h for f in self.fronts])
+        self.h = C.c_void_p()
+        _check(_lib().guber_mesh_create_local(arr, len(self.fronts), ring.h if ring is not None else None, max_n, C.byref(self.h)))
+
+    def eval_dev(self, gens, results):
+        """ctypes arrays of len(fronts) GuberBatch / GuberResult (device pointers on each rank's device, arrival order); asynchronous"""
+        _check(_lib().guber_mesh_eval_dev(self.h, gens, results))
+
+    def synchronize(self):
+        _check(_lib().guber_mesh_synchronize(self.h))
+
+    def stats(self):
+        st = MeshStats()
+        _check(_lib().guber_mesh_stats(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in MeshStats._fields_}
+
+    def close(self):
+        if getattr(self, "h", None):
+            _lib().guber_mesh_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # noqa: BLE001
+            pass

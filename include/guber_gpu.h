@@ -749,6 +749,37 @@ void guber_comm_destroy(guber_comm_t* c);
 int guber_global_sync(guber_comm_t* c, int64_t now_ms, guber_global_sync_stats_t* stats);       /* stats (optional): summed over the local ranks */
 int guber_comm_last_stats(guber_comm_t* c, uint32_t local_index, guber_global_sync_stats_t* out);   /* one local rank's share of the last sync */
 
+/* ---- a mesh of fronts: a stream that crosses ranks (gubernator.go:236-283).  Rank r is peer r of `ring` and owns fronts[r] (1 .. 16
+ *      engines of one device; ranks may share a device).  One call takes the generation that ARRIVED at every rank — gens[r], device
+ *      pointers on rank r's device, arrival order, possibly empty, one now_ms for all; is_owner, greg_expire and greg_duration NULL: the
+ *      ring decides ownership (replicated_hash.go:104-119), the calendar is the device's — and leaves results[r] in arrival order
+ *      (gubernator.proto:51-54), nothing behind n.
+ *        plain requests    evaluated on the owner's front with IsOwner (gubernator.go:247-256; forwarded ones: GetPeerRateLimits,
+ *                          gubernator.go:486 — behaviour bits unchanged, a NULL created_at becomes now_ms), answered where they arrived
+ *        order             the reference fans forwarded items out concurrently (gubernator.go:498) and fixes none between peers; here, per
+ *                          call, owner o evaluates the slices of source 0, 1, ... W-1 (its own in its place), each in arrival order
+ *        Behavior_GLOBAL   never forwarded (gubernator.go:258-270, 395-421): the arrival rank's front evaluates it with
+ *                          is_owner = (owner == r), on its global_engine if its rule names one
+ *        unplaceable keys  (empty, longer than the rank's max_key_bytes) stay and earn the front's item error
+ *        large inflows     an owner's inflow above its front's max_n goes to it as several generations, in order; never truncated
+ *      guber_mesh_create_local: every rank lives in this process, the transport is device-to-device copies on the receiver's stream (the
+ *      local mode of the GLOBAL exchange); a grouped ncclSend / ncclRecv transport and one rank per process are not built.  The host
+ *      waits only for the ranks' slice counts; the call returns when the answers' last hop is enqueued, guber_mesh_synchronize waits for it.
+ *      stats: forwarded = requests evaluated on another rank than they arrived at, bytes_moved = request and answer records that crossed
+ *      ranks, inflow_pieces = generations handed to the fronts, ms = wall time inside the calls. */
+typedef struct guber_mesh guber_mesh_t;
+typedef struct guber_mesh_stats {
+    uint64_t calls, requests, forwarded, bytes_moved, inflow_pieces;
+    double ms;
+} guber_mesh_stats_t;
+int guber_mesh_create_local(guber_front_t* const* fronts, uint32_t n_ranks, const guber_ring_t* ring,
+                            uint32_t max_n /* per rank and call */, guber_mesh_t** out);
+int guber_mesh_eval_dev(guber_mesh_t* m, const guber_batch_t* gens /* [n_ranks] */,
+                        guber_result_t* results /* [n_ranks] */);
+int guber_mesh_synchronize(guber_mesh_t* m);
+int guber_mesh_stats(guber_mesh_t* m, guber_mesh_stats_t* out);
+void guber_mesh_destroy(guber_mesh_t* m);
+
 /* ---- the daemon's time zone.  interval.go:97-142 build the civil dates of DURATION_IS_GREGORIAN intervals with now.Location():
  *      a "day" ends at 23:59:59.999 of the daemon's zone, not of UTC.  guber_set_timezone hands the engine that zone — the UTC
  *      offset in effect before the first listed transition and, per transition (ascending, at most 16), the instant in UTC seconds

@@ -8,6 +8,7 @@ of include/guber_gpu.h, so the same calls map one-to-one to cgo / JNI / N-API).
   3. the same through the protobuf wire format (what a daemon would hand over from the socket)
   4. the payload stage: what a gRPC handler thread calls with the raw bytes of its RPC — decode, routing to the GPU's tables, evaluation and the
      answers' order all on the device (guber_wire_pool_*)
+  5. two logical ranks behind a ring: a payload per rank, decoded on the device and answered through the mesh of fronts (guber_wire_dev_eval_mesh)
 """
 import os
 import sys
@@ -58,6 +59,27 @@ payload = req(b"requests_per_sec", b"account:7", 1, 2, 9_000) * 3 + req(b"mails_
 print("payload stage:", pool.get_rate_limits(payload).hex())
 print("stages so far:", pool.stats()["stages"])
 pool.close()
+
+# a stream that crosses ranks: two logical ranks of this GPU (two tables each) behind a consistent-hash ring; one payload arrives at each rank,
+# is decoded on the device, every item is evaluated on the rank the ring names and answered where its payload arrived
+ring = ga.Ring(["gpu0", "gpu1"], 512)
+rank_places = [ga.Placement(2), ga.Placement(2)]
+fronts = [ga.Front(tables[2 * r:2 * r + 2], rank_places[r], max_n=4096, depth=3) for r in range(2)]
+mesh = ga.Mesh(fronts, ring, 4096)
+decoders = [wire.DevWireDecoder(tables[2 * r], max_items=4096, max_payload_bytes=1 << 20, max_rpcs=16) for r in range(2)]
+for r, d in enumerate(decoders):
+    d.decode([req(b"requests_per_sec", b"account:%d" % k, 1, 2, 9_000) for k in (r, 5, 5)], now_ms)
+for r, answers in enumerate(wire.eval_mesh(decoders, mesh)):
+    print(f"rank {r} answers (status, limit, remaining, reset_time, err):", answers.rows())
+print("items evaluated on another rank than they arrived at:", mesh.stats()["forwarded"])
+for d in decoders:
+    d.close()
+mesh.close()
+for f in fronts:
+    f.close()
+for p in rank_places:
+    p.close()
+ring.close()
 for t in reversed(tables):
     t.close()
 place.close()

@@ -212,7 +212,7 @@ extern "C" int guber_profile_passes(guber_engine_t* e, float* us, uint32_t cap, 
 extern "C" const char* guber_last_error(void) { return g_last_error.c_str(); }
 
 #include "guber_global_sync.h"
-#include "guber_wire_dev.h"
+#include "guber_mesh.h"         // guber_mesh_*: a stream that crosses ranks — routed to its owning ranks on the device and answered where it arrived
+#include "guber_wire_dev.h"     // (behind the mesh: guber_wire_dev_eval_mesh feeds it)
 #include "guber_wire_pool.h"    // guber_wire_pool_*: the payload stage (caller threads hand over serialized RPCs)
 #include "guber_wire_pool_peer.h"   // guber_wire_pool_update_peer_globals: a broadcast of GLOBAL buckets installed through the pool's rule
-#include "guber_mesh.h"         // guber_mesh_*: a stream that crosses ranks — routed to its owning ranks on the device and answered where it arrived

@@ -22,6 +22,13 @@ namespace guber {
 //                back slice by slice in the order the requests left): sorted element j loads record j (coalesced), arrival position i
 //                takes it from LDS at lbase[dest] + rank (er[i]) and stores in arrival order
 // The front's lessons hold (guber_kernels_front.h): no per-workgroup tickets, no system-scope release at a kernel's end, no scratch.
+// KEYS.  k_mx_count and k_mx_pack are the two kernels that look at a key, and each exists twice: <false> finds request i's key packed
+// (key_bytes + key_off[i], key_off[i + 1] - key_off[i] bytes: what a caller of structure-of-arrays streams holds), <true> finds it in
+// ROWS (key_bytes + i * key_stride, key_len[i] bytes: what the device wire decoder leaves, guber_kernels_wire.h) — k_fr_count's rules
+// for rows: four words of a row are requested ahead only when the rows are 32 bytes apart or more (the guess is key_len[0]), a shorter
+// row's key is hashed from memory, and no byte outside [row, row + key_stride) is read: the padding behind a key is the caller's and
+// need not be zero.  A row cannot hold more than key_stride bytes: a key_len above it is an over-long key.  The form is the
+// instantiation's, not a branch: the packed kernels are what they were before rows existed (profiles/mesh_kernels.txt).
 // (dest[i], place[i]) of a request are er[i] and the tile's bases, as in the front: 2 bytes per request instead of 8.
 //
 // A request record: 64 bytes of columns, then the key row —
@@ -41,6 +48,7 @@ struct MxIn {
     const uint64_t* ring_hash; const uint8_t* ring_owner;          // the ring's sorted points (replicated_hash.go:90) and their peers
     uint16_t* er; uint8_t* own; uint32_t* tile_cnt; uint32_t* tile_base; FrontCtl* ctl; FrontHost* host;
     uint8_t* send; uint32_t rec_bytes;
+    uint32_t key_stride; const uint32_t* key_len;                   // <true> only: the rows' distance (a multiple of 8) and the keys' lengths
 };
 
 // fnv1 / fnv1a (segmentio/fasthash, as replicated_hash.go uses them) over a key of len < 32 bytes held in four words
@@ -57,7 +65,7 @@ __device__ __forceinline__ uint64_t mx_fnv_words4(const uint64_t (&w)[4], uint32
     return h;
 }
 
-__global__ __launch_bounds__(FR_TILE) void k_mx_count(MxIn A) {
+template <bool ROWS> __global__ __launch_bounds__(FR_TILE) void k_mx_count(MxIn A) {
     GUBER_DYN_LDS(smem);                                             // the ring's hashes (npts x 8 bytes) when they fit beside wtot
     __shared__ uint32_t wtot[FR_TILE / 64][MULTI_MEM_MAX];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, i = blockIdx.x * FR_TILE + tid;
@@ -73,11 +81,22 @@ __global__ __launch_bounds__(FR_TILE) void k_mx_count(MxIn A) {
     if (i < A.n) {
         // keys of one width: the key's words are requested where the first two offsets suggest, together with the request's own offsets,
         // and used if those confirm the guess (k_fr_count's way: one dependent trip less)
-        const uint32_t o0 = A.key_off[0], len0 = A.key_off[1] - o0, oend = A.key_off[A.n], off_g = o0 + i * len0;
+        // (rows: a row's place is known, key_len[0] is the guess, and 32 bytes of a row are readable only when the rows are that far apart)
+        uint32_t len0, off_g, off, len; bool spec;
         uint64_t kw[4] = {0, 0, 0, 0};
-        const bool spec = len0 != 0 && len0 < 32 && (uint64_t)o0 + (uint64_t)i * len0 + 32 <= (uint64_t)oend + 8;   // (a packed buffer is readable 8 bytes past the last key)
-        if (spec) { const uint8_t* kp = A.key_bytes + off_g; kw[0] = ld_key_word(kp); kw[1] = ld_key_word(kp + 8); kw[2] = ld_key_word(kp + 16); kw[3] = ld_key_word(kp + 24); }
-        const uint32_t off = A.key_off[i], len = A.key_off[i + 1] - off;
+        if constexpr (ROWS) {
+            len0 = A.key_len[0]; off_g = i * A.key_stride;
+            spec = len0 != 0 && len0 < 32 && A.key_stride >= 32u;
+            if (spec) { const uint8_t* kp = A.key_bytes + off_g; kw[0] = ld_key_word(kp); kw[1] = ld_key_word(kp + 8); kw[2] = ld_key_word(kp + 16); kw[3] = ld_key_word(kp + 24); }
+            off = off_g; len = A.key_len[i];
+            if (len > A.key_stride) len = A.max_key + 1u;            // (more than a row holds: over-long, never read)
+        } else {
+            const uint32_t o0 = A.key_off[0], oend = A.key_off[A.n];
+            len0 = A.key_off[1] - o0; off_g = o0 + i * len0;
+            spec = len0 != 0 && len0 < 32 && (uint64_t)o0 + (uint64_t)i * len0 + 32 <= (uint64_t)oend + 8;   // (a packed buffer is readable 8 bytes past the last key)
+            if (spec) { const uint8_t* kp = A.key_bytes + off_g; kw[0] = ld_key_word(kp); kw[1] = ld_key_word(kp + 8); kw[2] = ld_key_word(kp + 16); kw[3] = ld_key_word(kp + 24); }
+            off = A.key_off[i]; len = A.key_off[i + 1] - off;
+        }
         const bool stay = (A.behavior && (A.behavior[i] & 2u)) || len == 0 || len > A.max_key;
         // ReplicatedConsistentHash.Get (replicated_hash.go:104-119): the first point at or behind the key's hash, wrapping to point 0
         // (an over-long key is not hashed: nobody looks at the owner of a request that only earns its item error)
@@ -143,7 +162,7 @@ __global__ __launch_bounds__(FR_SCAN_T) void k_mx_scan(MxIn A, uint32_t nt, uint
 
 // LDS: the tile's requests in the destinations' order (2 KB) + FrTile.  Sorted element j gathers its request's columns (the tile's 1 024
 // requests: lines its neighbours load too) and writes record dofs[dest] + j: consecutive threads, consecutive records, whole sectors.
-__global__ __launch_bounds__(256) void k_mx_pack(MxIn A) {
+template <bool ROWS> __global__ __launch_bounds__(256) void k_mx_pack(MxIn A) {
     __shared__ FrTile T;
     __shared__ uint16_t src[FR_TILE];
     const uint32_t tile = blockIdx.x, tid = threadIdx.x, i0 = tile * FR_TILE + tid;
@@ -164,7 +183,10 @@ __global__ __launch_bounds__(256) void k_mx_pack(MxIn A) {
         if (dd[k] == 0xffffffffu) continue;
         const uint32_t i = tile * FR_TILE + src[tid + k * 256u];
         if (i >= A.n) continue;                                      // (cannot happen: the places are a permutation of the tile's requests)
-        const uint32_t off = A.key_off[i], len = A.key_off[i + 1] - off, lenc = len <= A.max_key ? len : A.max_key + 1u;
+        uint32_t off, len;
+        if constexpr (ROWS) { off = i * A.key_stride; len = A.key_len[i]; if (len > A.key_stride) len = A.max_key + 1u; }
+        else { off = A.key_off[i]; len = A.key_off[i + 1] - off; }
+        const uint32_t lenc = len <= A.max_key ? len : A.max_key + 1u;
         uint64_t* r = (uint64_t*)(A.send + (size_t)dd[k] * A.rec_bytes);
         r[0] = lenc | (uint64_t)(A.behavior ? A.behavior[i] : 0u) << 32;
         r[1] = (uint64_t)A.hits[i]; r[2] = (uint64_t)A.limit[i]; r[3] = (uint64_t)A.duration[i];
@@ -178,7 +200,8 @@ __global__ __launch_bounds__(256) void k_mx_pack(MxIn A) {
         const uint8_t* kp = A.key_bytes + off;
         for (uint32_t w = 0; w < nwr; ++w) {
             uint64_t v = 0ull;
-            if (w < nw) { v = ld_key_word(kp + 8 * w); if (w == nw - 1) v &= tail_mask(lenc - 8 * w); }   // (nothing is read more than 7 bytes behind the key)
+            // (packed: nothing is read more than 7 bytes behind the key; rows: a word that would start at or behind the row's end is zero, not loaded)
+            if (w < nw && (!ROWS || 8u * w < A.key_stride)) { v = ld_key_word(kp + 8 * w); if (w == nw - 1) v &= tail_mask(lenc - 8 * w); }
             r[8 + w] = v;
         }
     }

@@ -212,7 +212,7 @@ static int mesh_front_pieces(guber_mesh* m, guber_front* f, const FrontGen& g, c
     return front_eval(f, gens.data(), res.data(), (uint32_t)gens.size(), &done);
 }
 
-static int mesh_eval(guber_mesh* m, const guber_batch_t* gens, guber_result_t* results) {
+static int mesh_eval(guber_mesh* m, const guber_batch_t* gens, const guber_mesh_rows_t* rows, guber_result_t* results) {
     const uint32_t W = m->W;
     uint64_t total = 0;
     for (uint32_t r = 0; r < W; ++r) { m->ranks[r].n = gens[r].n; total += gens[r].n; clear_aggregates(results[r]); }
@@ -220,6 +220,7 @@ static int mesh_eval(guber_mesh* m, const guber_batch_t* gens, guber_result_t* r
     if (W == 1) {
         if (gens[0].n == 0) return 0;
         FrontGen g; g.b = gens[0];
+        if (rows && rows[0].key_stride) { g.key_stride = rows[0].key_stride; g.key_len = rows[0].key_len; }   // (the front takes rows itself)
         return mesh_front_pieces(m, m->ranks[0].f, g, results[0]);
     }
     if (++m->seq == 0) m->seq = 1;
@@ -235,10 +236,15 @@ static int mesh_eval(guber_mesh* m, const guber_batch_t* gens, guber_result_t* r
             A.n = b.n; A.seq = m->seq; A.now_ms = b.now_ms;
             A.key_bytes = b.key_bytes; A.key_off = b.key_off; A.hits = b.hits; A.limit = b.limit; A.duration = b.duration; A.burst = b.burst;
             A.created_at = b.created_at; A.behavior = b.behavior; A.algorithm = b.algorithm;
+            const bool in_rows = rows && rows[r].key_stride;         // (a rank's form is its own: each launches its own routing kernels)
+            A.key_stride = in_rows ? rows[r].key_stride : 0u; A.key_len = in_rows ? rows[r].key_len : nullptr;
             const uint32_t tiles = (b.n + FR_TILE - 1u) / FR_TILE;
-            hipLaunchKernelGGL(k_mx_count, dim3(tiles), dim3(FR_TILE), m->ring_lds ? (size_t)m->npts * 8 : 0, R.st, A);
+            const size_t ring_bytes = m->ring_lds ? (size_t)m->npts * 8 : 0;
+            if (in_rows) hipLaunchKernelGGL(k_mx_count<true>, dim3(tiles), dim3(FR_TILE), ring_bytes, R.st, A);
+            else hipLaunchKernelGGL(k_mx_count<false>, dim3(tiles), dim3(FR_TILE), ring_bytes, R.st, A);
             hipLaunchKernelGGL(k_mx_scan, dim3(MULTI_MEM_MAX / 4), dim3(FR_SCAN_T), 0, R.st, A, tiles, (tiles + FR_SCAN_T - 1) / FR_SCAN_T);
-            hipLaunchKernelGGL(k_mx_pack, dim3(tiles), dim3(256), 0, R.st, A);
+            if (in_rows) hipLaunchKernelGGL(k_mx_pack<true>, dim3(tiles), dim3(256), 0, R.st, A);
+            else hipLaunchKernelGGL(k_mx_pack<false>, dim3(tiles), dim3(256), 0, R.st, A);
             if (hipGetLastError() != hipSuccess) return fail(GUBER_E_HIP, "kernel launch");
         }
         HIPCHK(hipEventRecord(R.ev_pack, R.st));
@@ -303,10 +309,22 @@ static int mesh_eval(guber_mesh* m, const guber_batch_t* gens, guber_result_t* r
 
 // gens[r] -> results[r], r = 0 .. n_ranks-1: DEVICE pointers on rank r's device, requests and answers in arrival order.  Asynchronous like
 // guber_front_eval_dev: returns when the answers' last hop is enqueued (guber_mesh_synchronize waits).
-extern "C" int guber_mesh_eval_dev(guber_mesh_t* m, const guber_batch_t* gens, guber_result_t* results) {
+// rows[r].key_stride != 0: rank r's keys lie in ROWS (gens[r].key_bytes the first row, key_stride bytes apart, key_len[i] bytes of row i
+// are the key; gens[r].key_off NULL) — what the device wire decoder leaves; rows NULL or key_stride 0: packed.  Every check comes
+// before the first HIP call.
+extern "C" int guber_mesh_eval_rows_dev(guber_mesh_t* m, const guber_batch_t* gens, const guber_mesh_rows_t* rows, guber_result_t* results) {
     if (!m || !gens || !results) return fail(GUBER_E_INVALID_ARG, "null argument");
     for (uint32_t r = 0; r < m->W; ++r) {
-        const int rc = check_batch_args(&gens[r], &results[r]);
+        int rc;
+        if (rows && rows[r].key_stride) {
+            if (rows[r].key_stride & 7u) return fail(GUBER_E_INVALID_ARG, "key rows are a multiple of 8 bytes apart");
+            if (gens[r].key_off) return fail(GUBER_E_INVALID_ARG, "guber_mesh: key rows have no offsets (key_off must be NULL)");
+            if ((uint64_t)gens[r].n * rows[r].key_stride > 0xffffffffull) return fail(GUBER_E_BATCH_TOO_LARGE, "guber_mesh: a generation of key rows exceeds 4 GB");
+            const guber_batch_t& b = gens[r]; const guber_result_t& q = results[r];
+            rc = 0;                                                  // (check_batch_args with key_len in key_off's place)
+            if (b.n && (!b.key_bytes || !rows[r].key_len || !b.hits || !b.limit || !b.duration)) rc = fail(GUBER_E_INVALID_ARG, "batch is missing a mandatory array (key rows need key_len)");
+            else if (b.n && (!q.status || !q.limit || !q.remaining || !q.reset_time || !q.err)) rc = fail(GUBER_E_INVALID_ARG, "result is missing an array");
+        } else rc = check_batch_args(&gens[r], &results[r]);
         if (rc) return rc;
         if (gens[r].n > m->max_n) return fail(GUBER_E_BATCH_TOO_LARGE, "generation larger than the mesh was created for");
         if (gens[r].now_ms != gens[0].now_ms) return fail(GUBER_E_INVALID_ARG, "guber_mesh: the generations of a call carry one now_ms");
@@ -315,9 +333,13 @@ extern "C" int guber_mesh_eval_dev(guber_mesh_t* m, const guber_batch_t* gens, g
     }
     std::lock_guard<std::mutex> lk(m->mu);
     const auto t0 = std::chrono::steady_clock::now();
-    const int rc = mesh_eval(m, gens, results);
+    const int rc = mesh_eval(m, gens, rows, results);
     m->st.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return rc;
+}
+
+extern "C" int guber_mesh_eval_dev(guber_mesh_t* m, const guber_batch_t* gens, guber_result_t* results) {
+    return guber_mesh_eval_rows_dev(m, gens, nullptr, results);
 }
 
 extern "C" int guber_mesh_synchronize(guber_mesh_t* m) {

@@ -18,6 +18,7 @@ struct guber_wire_dev {
     DevBuf<uint2> d_went; uint32_t max_windows = 0;                                        // k_wire_win_a -> k_wire_win_b (8 KB per window of 8 KB)
     PinBuf<uint8_t> h_cols;                                                              // read-back of the decoded columns (tests, response encoding)
     uint32_t nrpc = 0, n_items = 0; int64_t now_ms = 0;
+    bool peer_rpc = false;                                                                 // the last decode carried a GUBER_WIRE_RPC_PEER payload (guber_wire_dev_eval_mesh refuses it)
     guber::WireIn in{}; guber::WireScratch sc{}; guber::WireOut out{};
     // the asynchronous calls (guber_wire_dev_*_async / _poll: the payload stage of guber_wire_pool.h): a stream of the caller's for the
     // decode, one event for "the decode's verdicts are in host memory", one for "the answers are where the caller wanted them"
@@ -86,6 +87,7 @@ static int wire_dev_decode_enqueue(guber_wire_dev* d, uint32_t nrpc, size_t lo, 
     uint8_t* h_owner = (uint8_t*)(h_off + 3 * R + 1);
     hipStream_t st = d->stream();
     if (is_owner) memcpy(h_owner, is_owner, nrpc); else memset(h_owner, 1, nrpc);
+    for (uint32_t r = 0; is_owner && r < nrpc; ++r) if (is_owner[r] & GUBER_WIRE_RPC_PEER) d->peer_rpc = true;
     // ONE copy — the decode's arguments (off | len | wfirst | owner) and, behind them, the payload bytes up to the last payload's end — then the
     // kernels; the verdicts come back through k_wire_kill's stores into host memory: no copy, no memset behind or between (every command costs
     // the stream ~5 us; what lies between the arguments and the first payload of a caller that staged at an offset travels along unread)
@@ -145,7 +147,7 @@ extern "C" int guber_wire_dev_decode(guber_wire_dev_t* d, const uint8_t* const* 
     guber_engine* e = d->e;
     std::lock_guard<std::mutex> lk(e->mu);
     if (e->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
-    d->nrpc = nrpc; d->n_items = 0; d->now_ms = now_ms;
+    d->nrpc = nrpc; d->n_items = 0; d->now_ms = now_ms; d->peer_rpc = false;
     if (!nrpc) return GUBER_OK;
     uint32_t* h_off = d->h_meta(); uint32_t* h_len = h_off + d->max_rpcs; uint32_t* h_wfirst = h_off + 2 * (size_t)d->max_rpcs;
     size_t pos = 0;
@@ -186,7 +188,7 @@ static int wire_dev_decode_staged_any(guber_wire_dev_t* d, const uint32_t* offs,
     std::unique_lock<std::mutex> lk(e->mu, std::defer_lock);
     if (!d->own) lk.lock();
     if (d->own ? hipSetDevice(e->device) != hipSuccess : e->set_device() != 0) return fail(GUBER_E_HIP, "hipSetDevice");
-    d->nrpc = nrpc; d->n_items = 0; d->now_ms = now_ms;
+    d->nrpc = nrpc; d->n_items = 0; d->now_ms = now_ms; d->peer_rpc = false;
     if (!nrpc) return GUBER_OK;
     uint32_t* h_off = d->h_meta(); uint32_t* h_len = h_off + d->max_rpcs; uint32_t* h_wfirst = h_off + 2 * (size_t)d->max_rpcs;
     uint32_t windows = 0;
@@ -323,6 +325,71 @@ extern "C" int guber_wire_dev_eval_front(guber_wire_dev_t* d, guber_front_t* f, 
     HIPCHK(hipMemcpyAsync(r->remaining, d->d_out64.p + M, (size_t)n * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(r->reset_time, d->d_out64.p + 2 * M, (size_t)n * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    return GUBER_OK;
+}
+// The decoded batches of one decoder per rank through a MESH of fronts (guber_mesh.h): decs[r]'s last decode is the generation that arrived
+// at rank r — its key rows as they lie (guber_mesh_eval_rows_dev: k_mx_count<true> / k_mx_pack<true> read rows), its columns, the decode's
+// now_ms — every item is evaluated on the rank the ring names (gubernator.go:236-283) and answered, in the order of the RPCs' items, where
+// its payload arrived; results[r]: HOST arrays of decs[r]'s n_items entries.  Synchronous, as guber_wire_dev_eval_front.  The decoder's
+// per-item is_owner is not handed on (the ring decides), which is why a decode with a peer RPC in it is refused: its items are evaluated
+// where they arrive (gubernator.go:486) — guber_wire_dev_eval_front's job.  Pre-rejected items and dead slots have empty key rows: they
+// stay, keep their place and earn the front's item error.  Every refusal comes before anything is enqueued.
+extern "C" int guber_wire_dev_eval_mesh(guber_wire_dev_t* const* decs, guber_mesh_t* m, guber_result_t* results) {
+    if (!decs || !m || !results) return fail(GUBER_E_INVALID_ARG, "null argument");
+    const uint32_t W = m->W;
+    int64_t now_ms = 0; bool have_now = false;
+    for (uint32_t r = 0; r < W; ++r) {
+        guber_wire_dev* d = decs[r];
+        if (!d) continue;
+        for (uint32_t q = 0; q < r; ++q) if (decs[q] == d) return fail(GUBER_E_INVALID_ARG, "guber_wire_dev_eval_mesh: a decoder at two ranks");
+        if (d->dec_pending || d->eval_pending || d->routed) return fail(GUBER_E_INVALID_ARG, "the decoder's previous asynchronous call has not been collected");
+        if (d->peer_rpc) return fail(GUBER_E_INVALID_ARG, "guber_wire_dev_eval_mesh: a peer RPC's items are evaluated where they arrive (guber_wire_dev_eval_front)");
+        if (d->e->device != m->ranks[r].f->device) return fail(GUBER_E_INVALID_ARG, "guber_wire_dev_eval_mesh: a decoder on another device than its rank's front");
+        if (!d->n_items) continue;
+        if (d->n_items > m->max_n) return fail(GUBER_E_BATCH_TOO_LARGE, "more items than the mesh's generations hold");
+        if (have_now && d->now_ms != now_ms) return fail(GUBER_E_INVALID_ARG, "guber_wire_dev_eval_mesh: the decodes of a call carry one now_ms");
+        now_ms = d->now_ms; have_now = true;
+        const guber_result_t& q = results[r];
+        if (!q.status || !q.limit || !q.remaining || !q.reset_time || !q.err) return fail(GUBER_E_INVALID_ARG, "result is missing an array");
+    }
+    std::vector<guber_batch_t> gens(W, guber_batch_t{}); std::vector<guber_mesh_rows_t> rows(W, guber_mesh_rows_t{}); std::vector<guber_result_t> dr(W, guber_result_t{});
+    for (uint32_t r = 0; r < W; ++r) {
+        guber_result_t& q = results[r];
+        q.over_limit_count = q.cache_hits = q.cache_misses = q.unexpired_evictions = 0; q.cache_size = 0;
+        gens[r].now_ms = now_ms;
+        guber_wire_dev* d = decs[r];
+        if (!d || !d->n_items) continue;
+        FrontGen g;
+        wire_dev_front_gen(d, g);
+        gens[r] = g.b; gens[r].is_owner = nullptr;
+        rows[r].key_stride = g.key_stride; rows[r].key_len = g.key_len;
+        const size_t M = d->max_items;
+        dr[r].status = d->d_out8.p; dr[r].err = d->d_out8.p + M; dr[r].limit = d->d_out64.p; dr[r].remaining = d->d_out64.p + M; dr[r].reset_time = d->d_out64.p + 2 * M;
+    }
+    {   // (every decode was synchronised on its stream: guber_wire_dev_decode* read its verdicts back)
+        const int rc = guber_mesh_eval_rows_dev(m, gens.data(), rows.data(), dr.data());
+        if (rc) return rc;
+    }
+    {
+        const int rc = guber_mesh_synchronize(m);
+        if (rc) return rc;
+    }
+    for (uint32_t r = 0; r < W; ++r) {
+        guber_wire_dev* d = decs[r];
+        if (!d || !d->n_items) continue;
+        const size_t n = d->n_items, M = d->max_items;
+        guber_engine* e = d->e;
+        std::lock_guard<std::mutex> lk(e->mu);
+        if (e->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
+        hipStream_t st = d->stream();
+        const guber_result_t& q = results[r];
+        HIPCHK(hipMemcpyAsync(q.status, d->d_out8.p, n, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(q.err, d->d_out8.p + M, n, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(q.limit, d->d_out64.p, n * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(q.remaining, d->d_out64.p + M, n * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(q.reset_time, d->d_out64.p + 2 * M, n * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
     return GUBER_OK;
 }
 // guber_wire_dev_eval_front_async   the same, enqueued only: `r`'s arrays are DEVICE-VISIBLE (HBM, or host memory the device writes in

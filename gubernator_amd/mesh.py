@@ -11,6 +11,12 @@ class MeshStats(C.Structure):
                 ("inflow_pieces", C.c_uint64), ("ms", C.c_double)]
 
 
+class MeshRows(C.Structure):
+    """guber_mesh_rows_t: key_stride 0 = the rank's generation is packed; otherwise its keys lie in rows key_stride bytes apart (a
+    multiple of 8) and key_len is a device array of the keys' lengths"""
+    _fields_ = [("key_stride", C.c_uint32), ("key_len", C.c_void_p)]
+
+
 _bound = False
 
 
@@ -20,6 +26,7 @@ def _lib():
     if not _bound:
         L.guber_mesh_create_local.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
         L.guber_mesh_eval_dev.argtypes = [C.c_void_p, C.POINTER(GuberBatch), C.POINTER(GuberResult)]
+        L.guber_mesh_eval_rows_dev.argtypes = [C.c_void_p, C.POINTER(GuberBatch), C.POINTER(MeshRows), C.POINTER(GuberResult)]
         L.guber_mesh_synchronize.argtypes = [C.c_void_p]
         L.guber_mesh_stats.argtypes = [C.c_void_p, C.POINTER(MeshStats)]
         L.guber_mesh_destroy.argtypes = [C.c_void_p]
@@ -47,6 +54,11 @@ class Mesh:
     def eval_dev(self, gens, results):
         """ctypes arrays of len(fronts) GuberBatch / GuberResult (device pointers on each rank's device, arrival order); asynchronous"""
         _check(_lib().guber_mesh_eval_dev(self.h, gens, results))
+
+    def eval_rows_dev(self, gens, rows, results):
+        """eval_dev for generations whose keys lie in rows: `rows` a ctypes array of len(fronts) MeshRows (None: every rank packed); rank
+        r with rows[r].key_stride != 0 has gens[r].key_bytes = its first row and gens[r].key_off = None"""
+        _check(_lib().guber_mesh_eval_rows_dev(self.h, gens, rows, results))
 
     def synchronize(self):
         _check(_lib().guber_mesh_synchronize(self.h))

@@ -16,7 +16,7 @@ WIRE_SYMBOLS = [
     "guber_wire_eval", "guber_wire_encode_bound", "guber_wire_encode_responses", "guber_wire_encode_peer_responses",
     "guber_wire_items_create", "guber_wire_items_destroy", "guber_wire_decode_globals", "guber_wire_encode_globals",
     "guber_wire_dev_create", "guber_wire_dev_destroy", "guber_wire_dev_decode", "guber_wire_dev_buffer", "guber_wire_dev_decode_staged",
-    "guber_wire_dev_eval", "guber_wire_dev_eval_front", "guber_wire_dev_columns",
+    "guber_wire_dev_eval", "guber_wire_dev_eval_front", "guber_wire_dev_eval_mesh", "guber_wire_dev_columns",
     "guber_wire_dev_set_stream", "guber_wire_dev_decode_staged_async", "guber_wire_dev_decode_collect", "guber_wire_dev_eval_front_async",
     "guber_wire_dev_eval_collect", "guber_wire_dev_route_front_async", "guber_wire_dev_route_ready",
     "guber_wire_pool_create", "guber_wire_pool_destroy", "guber_wire_pool_get_rate_limits", "guber_wire_pool_response_bound",
@@ -299,6 +299,23 @@ class DevWireDecoder:
         if getattr(self, "h", None):
             self.L.guber_wire_dev_destroy(self.h)
             self.h = None
+
+
+def eval_mesh(decoders, mesh):
+    """guber_wire_dev_eval_mesh: decoders[r] (a DevWireDecoder, or None: nothing arrived at rank r) holds the decode of the payloads that
+    arrived at rank r of `mesh`; every item is evaluated on the rank the ring names and answered where it arrived -> one HostResult per
+    rank, of the rank's n_items entries"""
+    from .abi import HostResult
+    L = _lib()
+    L.guber_wire_dev_eval_mesh.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(GuberResult)]
+    W = len(decoders)
+    decs = (C.c_void_p * max(W, 1))(*[d.h if d is not None else None for d in decoders])
+    out = [HostResult(getattr(d, "n", 0) if d is not None else 0) for d in decoders]
+    res = (GuberResult * max(W, 1))(*[r.c for r in out])
+    rc = L.guber_wire_dev_eval_mesh(decs, mesh.h, res)
+    if rc:
+        raise GuberError(rc, lib().guber_last_error().decode())
+    return out
 
 
 class WirePoolConfig(C.Structure):

@@ -766,7 +766,15 @@ int guber_comm_last_stats(guber_comm_t* c, uint32_t local_index, guber_global_sy
  *      local mode of the GLOBAL exchange); a grouped ncclSend / ncclRecv transport and one rank per process are not built.  The host
  *      waits only for the ranks' slice counts; the call returns when the answers' last hop is enqueued, guber_mesh_synchronize waits for it.
  *      stats: forwarded = requests evaluated on another rank than they arrived at, bytes_moved = request and answer records that crossed
- *      ranks, inflow_pieces = generations handed to the fronts, ms = wall time inside the calls. */
+ *      ranks, inflow_pieces = generations handed to the fronts, ms = wall time inside the calls.
+ *      guber_mesh_eval_rows_dev: the same call for generations whose keys lie in ROWS — what the device wire decoder leaves
+ *      (include/guber_wire.h: guber_wire_dev_eval_mesh is this call fed by decoders).  rows NULL, or rows[r].key_stride == 0: rank r's
+ *      generation is packed (key_bytes + key_off), as guber_mesh_eval_dev takes it; ranks may differ within one call.  Otherwise
+ *      gens[r].key_bytes is the first row, key i = key_bytes + i * key_stride with key_len[i] bytes, gens[r].key_off is NULL, key_stride
+ *      is a multiple of 8, key_len a device array of gens[r].n entries on rank r's device, and n * key_stride fits in 32 bits.  No byte
+ *      outside a row is read and the padding behind a key need not be zero; a key_len above key_stride is an over-long key.  Owner,
+ *      answers, residency, order, statistics and asynchrony do not depend on the form.  guber_mesh_eval_dev(m, g, r) is
+ *      guber_mesh_eval_rows_dev(m, g, NULL, r). */
 typedef struct guber_mesh guber_mesh_t;
 typedef struct guber_mesh_stats {
     uint64_t calls, requests, forwarded, bytes_moved, inflow_pieces;
@@ -776,6 +784,10 @@ int guber_mesh_create_local(guber_front_t* const* fronts, uint32_t n_ranks, cons
                             uint32_t max_n /* per rank and call */, guber_mesh_t** out);
 int guber_mesh_eval_dev(guber_mesh_t* m, const guber_batch_t* gens /* [n_ranks] */,
                         guber_result_t* results /* [n_ranks] */);
+typedef struct guber_mesh_rows { uint32_t key_stride; const uint32_t* key_len; } guber_mesh_rows_t;
+int guber_mesh_eval_rows_dev(guber_mesh_t* m, const guber_batch_t* gens /* [n_ranks] */,
+                             const guber_mesh_rows_t* rows /* [n_ranks], NULL = every rank packed */,
+                             guber_result_t* results /* [n_ranks] */);
 int guber_mesh_synchronize(guber_mesh_t* m);
 int guber_mesh_stats(guber_mesh_t* m, guber_mesh_stats_t* out);
 void guber_mesh_destroy(guber_mesh_t* m);

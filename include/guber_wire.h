@@ -150,6 +150,9 @@ int guber_wire_encode_globals(const uint8_t* key_bytes, const uint32_t* key_off,
  *                           last): a receive path that reads its sockets straight into the buffer skips guber_wire_dev_decode's copy
  *   guber_wire_dev_eval     the batch through the engine (as guber_eval_batch_dev), results to host arrays of n_items entries
  *   guber_wire_dev_eval_front  the batch through a front over several engines: decode, routing, evaluation and the answers' order in HBM
+ *   guber_wire_dev_eval_mesh   the last decodes of one decoder per rank through a mesh of fronts (include/guber_gpu.h guber_mesh_*): every
+ *                           item is evaluated on the rank the ring names and answered where its payload arrived — the decision WHERE a
+ *                           payload's items go (gubernator.go:236-283), taken on the device
  *   guber_wire_dev_columns  the decoded columns copied to host memory (keys as rows of key_stride bytes + key_len): what
  *                           guber_wire_encode_responses-style code and the tests read */
 #define GUBER_WIRE_PRE_DEAD 255
@@ -172,6 +175,16 @@ int guber_wire_dev_eval(guber_wire_dev_t* d, guber_result_t* r);
 /* the decoded batch through a front (include/guber_gpu.h guber_front_*) instead: routed to the front's engines on the device, evaluated there,
  * answered in the order of the RPCs' items; results to host arrays of n_items entries (n_items <= the front's max_n) */
 int guber_wire_dev_eval_front(guber_wire_dev_t* d, guber_front_t* f, guber_result_t* r);
+/* the decoded batches of decs[r] — the payloads that ARRIVED at rank r; NULL, or nothing decoded: nothing arrived there — through a mesh of
+ * fronts: each decoder's last decode is its rank's generation (its key rows, its columns, the decode's now_ms) for guber_mesh_eval_rows_dev;
+ * synchronous: results[r] are HOST arrays of decs[r]'s n_items entries, answered in the order of the RPCs' items, aggregate counters zero.
+ * The ring decides ownership, so the decoder's per-item is_owner is not handed on: a decode that carried a GUBER_WIRE_RPC_PEER payload is
+ * refused (a peer RPC's items are evaluated where they arrive, gubernator.go:486: guber_wire_dev_eval_front).  Pre-rejected items and the
+ * dead slots of a rejected RPC have empty keys: they stay on their arrival rank, keep their place and earn the front's item error.
+ * GUBER_E_INVALID_ARG before anything is enqueued: a NULL argument, a decoder with an uncollected asynchronous call, the same decoder at
+ * two ranks, a decoder whose engine is on another device than its rank's front, two non-empty decoders with different now_ms, a missing
+ * result array where n_items > 0; GUBER_E_BATCH_TOO_LARGE: n_items above the mesh's max_n. */
+int guber_wire_dev_eval_mesh(guber_wire_dev_t* const* decs /* [n_ranks] */, guber_mesh_t* m, guber_result_t* results /* [n_ranks] */);
 int guber_wire_dev_columns(guber_wire_dev_t* d, guber_wire_columns_t* c);
 /* The same in two halves each, for a caller that keeps several decoders busy and never blocks on the GPU (the payload stage below):
  *   guber_wire_dev_set_stream           the decode's copies and kernels go to `stream` (hipStream_t) instead of the engine's stream
@@ -230,7 +243,8 @@ int guber_wire_dev_route_ready(guber_wire_dev_t* d, guber_front_t* f);
  *                                     in ms, as the reference's tests use clock.Freeze
  *   What this surface does NOT do: the Store's write-through callbacks (store.go:49-65: guber_pool_set_store / guber_eval_batch_store — a daemon
  *   with conf.Store keeps the per-request pool) (the front below it has it: guber_front_eval_store_dev), metadata propagation (RateLimitReq.metadata is skipped), and the decision WHERE a payload goes
- *   (forwarding to the owning peer, gubernator.go:236-283: the Go front end hands over only what this instance evaluates).  Behavior_GLOBAL items
+ *   (forwarding to the owning peer, gubernator.go:236-283: the threaded pool still evaluates only what its instance owns, the Go front end hands
+ *   over just that; the synchronous building block that takes the decision on the device is guber_wire_dev_eval_mesh above).  Behavior_GLOBAL items
  *   are evaluated on their table and queued for the GLOBAL exchange by the engine as on every other entry point (guber_global_take / _sync);
  *   a rule whose global_engine is set sends them to the device's GLOBAL engine. */
 typedef struct guber_wire_pool guber_wire_pool_t;

@@ -151,3 +151,44 @@ GW_HD bool parse_req(const uint8_t* p, const uint8_t* end, ReqFields& f) {
 }
 
 }}  // namespace guber::wire
+
+// ---- the payload stage's item bound (host only: guber_wire_pool.h's callers, before their RPC joins a stage; here so that the wire fuzz
+// compiles the same text beside the decoders it has to agree with)
+#ifndef GUBER_WPL_WALK_MAX
+#define GUBER_WPL_WALK_MAX 8192       // payloads shorter than this have their records counted; longer ones are bounded by the cap
+#endif
+// the top-level chain of a message walked: how many field-1 LEN records it holds.  EXACT for every message the decoders accept (scan_toplevel,
+// guber_wire_decode_requests): unknown fields are skipped by wire type and a group the way wire::skip_field skips it — to the matching
+// END_GROUP, nested groups included, nothing inside counted.  Never LOW for any other: where the chain cannot be followed (an unknown field
+// that runs past the end, a group that does not close, a stray END_GROUP, wire types 6 / 7 — the decoders turn such a message away whole) the
+// answer is the records so far plus one per two bytes left, the most a chain can hold.  A plain record costs a tag, a length and a skip.
+inline uint32_t wpl_count_records(const uint8_t* p, size_t len) {
+    const uint8_t* end = p + len;
+    size_t n = 0;
+    while (p < end) {
+        const uint8_t* at = p;
+        uint64_t tag = 0; int sh = 0;
+        while (p < end && sh < 64) { const uint8_t b = *p++; tag |= (uint64_t)(b & 0x7f) << sh; sh += 7; if (!(b & 0x80)) break; }
+        const uint32_t wt = (uint32_t)(tag & 7);
+        if (wt == 2) {
+            uint64_t L = 0; sh = 0;
+            while (p < end && sh < 64) { const uint8_t b = *p++; L |= (uint64_t)(b & 0x7f) << sh; sh += 7; if (!(b & 0x80)) break; }
+            if ((tag >> 3) == 1) ++n;
+            if (L > (uint64_t)(end - p)) break;                        // (runs past the end: counted, and nothing can follow it)
+            p += L;
+            continue;
+        }
+        bool ok;
+        if (wt == 0) { while (p < end && (*p & 0x80)) ++p; ok = p < end; p += ok; }
+        else if (wt == 1) { ok = end - p >= 8; p += ok ? 8 : 0; }
+        else if (wt == 5) { ok = end - p >= 4; p += ok ? 4 : 0; }
+        else ok = wt == 3 && guber::wire::skip_field(p, end, 3, tag >> 3);
+        if (!ok) { n += (size_t)(end - at) / 2; break; }
+    }
+    return n > 0xffffffffull ? 0xffffffffu : (uint32_t)n;
+}
+inline uint32_t wpl_item_bound(const uint8_t* p, size_t len, uint32_t cap) {
+    if (len >= GUBER_WPL_WALK_MAX) { const size_t most = len / 2; return most < cap ? (uint32_t)most : cap; }
+    const uint32_t n = wpl_count_records(p, len);
+    return n < cap ? n : cap;
+}

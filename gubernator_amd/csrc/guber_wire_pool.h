@@ -31,9 +31,8 @@
 #include <sys/resource.h>
 #include <climits>
 
-#ifndef GUBER_WPL_WALK_MAX
-#define GUBER_WPL_WALK_MAX 8192       // payloads shorter than this have their records counted; longer ones are bounded by the cap
-#endif
+#include "guber_wire_parse.h"         // wpl_item_bound / wpl_count_records, GUBER_WPL_WALK_MAX
+
 namespace {
 constexpr uint64_t WPL_CLOSED = 1ull << 63;
 constexpr uint32_t WPL_MAX_RPCS = 4095, WPL_MAX_ITEMS = (1u << 20) - 1, WPL_MAX_B16 = (1u << 20) - 1, WPL_NONE = 15, WPL_MAX_STAGES = 12;
@@ -55,35 +54,14 @@ inline void wpl_relax() {
     __builtin_ia32_pause();
 #endif
 }
-// how many RateLimitReq records a payload can hold at most: the top-level chain walked for short payloads (exact when well-formed), the cap for
-// long ones (an RPC with more than the cap is turned away whole and takes no place: gubernator.go:189-193).  Counting the records of EVERY
-// payload (a tag, a length and a skip per record: ~3 us for 1000) would keep stages full when long RPCs hold few, long requests, and was
-// measured on full ones: -3 ... -4 % at every caller count (profiles/r06_wire_pool.txt) — the bound of a long payload stays the cap.
-// the top-level chain of a message walked: how many field-1 records it holds (exact when the message is well-formed)
-inline uint32_t wpl_count_records(const uint8_t* p, size_t len) {
-    const uint8_t* end = p + len;
-    uint32_t n = 0;
-    while (p < end) {
-        uint64_t tag = 0; int sh = 0;
-        while (p < end && sh < 64) { const uint8_t b = *p++; tag |= (uint64_t)(b & 0x7f) << sh; sh += 7; if (!(b & 0x80)) break; }
-        const uint32_t wt = (uint32_t)(tag & 7);
-        if (wt == 0) { while (p < end && (*p++ & 0x80)) {} }
-        else if (wt == 1) p += 8;
-        else if (wt == 5) p += 4;
-        else if (wt == 2) {
-            uint64_t L = 0; sh = 0;
-            while (p < end && sh < 64) { const uint8_t b = *p++; L |= (uint64_t)(b & 0x7f) << sh; sh += 7; if (!(b & 0x80)) break; }
-            if ((tag >> 3) == 1) ++n;
-            if (L > (uint64_t)(end - p)) break;
-            p += L;
-        } else break;                                                  // (groups, reserved wire types: the decoders turn the payload away)
-    }
-    return n;
-}
-inline uint32_t wpl_item_bound(const uint8_t* p, size_t len, uint32_t cap) {
-    if (len >= GUBER_WPL_WALK_MAX) return (uint32_t)std::min<size_t>(cap, len / 2);
-    return std::min(wpl_count_records(p, len), cap);
-}
+// how many RateLimitReq records a payload can hold at most — wpl_item_bound / wpl_count_records (guber_wire_parse.h, beside the decoders they
+// agree with): the top-level chain walked for short payloads (exact for every message the decoders accept, groups skipped as they skip them;
+// never low for the others), the cap for long ones (an RPC with more than the cap is turned away whole and takes no place:
+// gubernator.go:189-193).  The bound is the places the RPC reserves in its stage, sizes guber_wire_pool_response_bound() and decides whether
+// the caller evaluates the RPC itself: a bound BELOW what the device delivers overfills the stage (wire_number_batch then turns other callers'
+// RPCs away) and undersizes the caller's buffer.  Counting the records of EVERY payload (a tag, a length and a skip per record: ~3 us for 1000)
+// would keep stages full when long RPCs hold few, long requests, and was measured on full ones: -3 ... -4 % at every caller count
+// (profiles/r06_wire_pool.txt) — the bound of a long payload stays the cap.
 // the CPUs this process may really use: the affinity mask, capped by the cgroup's quota (cpu.max) — a container on a 256-thread host with a
 // quota of 16 has 16
 inline uint32_t wpl_usable_cpus() {

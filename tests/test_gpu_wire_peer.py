@@ -18,6 +18,7 @@ import gubernator_amd as ga
 import scenarios
 import support
 import wire_replay
+import wire_shapes
 from gubernator_amd import wire as gw
 from pb_schema import PB
 from test_wire_cpu import NOW, rand_reqs
@@ -199,6 +200,28 @@ def test_peer_messages_that_are_turned_away_whole(n_plain, with_global):
         assert ei.value.code == -20
     assert rig.size() == 0
     assert len(wire_replay.rows_of(rig.pool.get_peer_rate_limits(good))) == 50 and rig.size() > 0
+    rig.close()
+
+
+def test_unusual_but_valid_peer_messages_get_the_peer_transcoders_bytes():
+    """tests/wire_shapes.py's well-formed payloads (unknown fields, groups, padded lengths; tests/test_gpu_wire_pool.py has the client RPC)
+    through guber_wire_pool_get_peer_rate_limits with the default response buffer — among them the 300 requests of limit 2^62 behind an
+    empty group, whose answers are longer than the request: the peer transcoder's bytes around the oracle, one row per top-level record"""
+    rng = np.random.default_rng(77)
+    rig = Rig(4, False)
+    shapes = wire_shapes.well_formed()
+    assert wire_shapes.GROUP_LED_300 in dict(shapes)
+    now = NOW
+    for k in rng.permutation(len(shapes)):
+        label, payload = shapes[int(k)]
+        try:
+            got = rig.call(payload, now, True)
+        except ga.GuberError as e:
+            pytest.fail(f"{label}: turned away with {e.code} ({e})")
+        assert got == rig.expected(payload, now, True), label
+        assert len(wire_replay.rows_of(got)) == wire_shapes.n_records(label), label
+        now += int(rng.integers(0, 900))
+    assert rig.size() == rig.o.size()                            # (no validation on this path: "ws_" is a bucket like any other)
     rig.close()
 
 

@@ -14,6 +14,7 @@ import gubernator_amd as ga
 import scenarios
 import support
 import wire_replay
+import wire_shapes
 from gubernator_amd import wire as gw
 from test_wire_cpu import NOW, rand_reqs
 
@@ -350,3 +351,131 @@ def test_fuzzed_payloads_get_the_host_transcoders_verdict_and_bytes():
         e.close()
     place.close()
     o.close(); wb.close()
+
+
+@pytest.mark.parametrize("n_engines", [1, 3])
+def test_unusual_but_valid_messages_get_the_host_transcoders_bytes(n_engines):
+    """tests/wire_shapes.py's well-formed payloads — unknown fields of every wire type and tag width, field 1 with another wire type, padded
+    length varints, groups empty / filled with what looks like records / nested / of wide field numbers, each first, in the middle and last
+    among 1 .. 4 records (the caller's own evaluation), 5, 60 and 300 (a stage), and across the edge of the first 8 192 bytes of a longer
+    payload (the device's windowed walk) — one RPC after the other with the DEFAULT response buffer, guber_wire_pool_response_bound(): the
+    host walk that sizes it and reserves the RPC's places (wpl_item_bound) has to count what the device decoder delivers.  Every response
+    equals the host transcoder's around ONE oracle byte for byte and has one row per top-level record: what a group holds is no item.
+    Among them the RPC of 300 requests of limit 2^62 behind an empty group: 8 700 bytes of answers to 7 802 of request — with a walk that
+    stops at the group the buffer is 7 818 bytes and the call says GUBER_E_NOMEM (-6) after the decisions have been applied."""
+    rng = np.random.default_rng(41 + n_engines)
+    shapes = wire_shapes.well_formed()
+    engs = _engines(n_engines, cache_size=1 << 16, max_batch=8192, max_key_bytes=256)
+    place = ga.Placement(n_engines) if n_engines > 1 else None
+    pool = gw.WirePool(engs, place, **SMALL)
+    o = support.Oracle(cache_size=1 << 20)
+    wb = gw.WireBatch(4096, 1 << 20)
+    now = NOW
+    rows_seen = errors_seen = over_limit = 0
+    for k in rng.permutation(len(shapes)):
+        label, payload = shapes[int(k)]
+        pool.set_clock(now)
+        try:
+            got = pool.get_rate_limits(payload)
+        except ga.GuberError as e:
+            pytest.fail(f"{label}: turned away with {e.code} ({e})")
+        assert got == _expected(o, wb, payload, now), label
+        rows = wire_replay.rows_of(got)
+        assert len(rows) == wire_shapes.n_records(label), label
+        if label == wire_shapes.GROUP_LED_300:
+            assert len(payload) == 7802 and len(got) == 8700
+        rows_seen += len(rows); errors_seen += sum(1 for r in rows if r[4]); over_limit += sum(1 for r in rows if r[0] == 1)
+        now += int(rng.integers(0, 900))
+    assert rows_seen == sum(wire_shapes.n_records(label) for label, _ in shapes)
+    assert errors_seen == len(wire_shapes.ELEMENTS) and over_limit > 100      # (the host transcoder's encoding and buckets that ran dry were among them)
+    # (the oracle gives the items without a key a bucket of their own; the engines never let them near one)
+    assert sum(e.size() for e in engs) == o.size() - 1
+    pool.close()
+    for e in reversed(engs):
+        e.close()
+    if place:
+        place.close()
+    o.close(); wb.close()
+
+
+def test_messages_with_broken_groups_are_turned_away_whole():
+    """the malformed siblings of tests/wire_shapes.py — a group that does not end, one ended by another field's END_GROUP, a stray END_GROUP,
+    70 groups inside each other, wire types 6 and 7 — before, between and behind 2 records (its caller would evaluate such an RPC) and 20 (a
+    stage): GUBER_E_WIRE_MALFORMED every time, nothing of any of them reaches a bucket, and the pool answers the next RPC"""
+    rng = np.random.default_rng(6)
+    engs = _engines(2, cache_size=1 << 16, max_batch=8192, max_key_bytes=128)
+    place = ga.Placement(2)
+    pool = gw.WirePool(engs, place, **SMALL)
+    pool.set_clock(NOW)
+    shapes = wire_shapes.malformed()
+    assert len(shapes) >= 30
+    for label, payload in shapes:
+        with pytest.raises(ga.GuberError) as ei:
+            pool.get_rate_limits(payload)
+        assert ei.value.code == -20, label                       # GUBER_E_WIRE_MALFORMED
+        assert sum(e.size() for e in engs) == 0, label
+    good = wire_replay.pb_request(rand_reqs(rng, 50, bad=False))
+    assert len(wire_replay.rows_of(pool.get_rate_limits(good))) == 50 and sum(e.size() for e in engs) > 0
+    pool.close()
+    for e in reversed(engs):
+        e.close()
+    place.close()
+
+
+def test_callers_with_unknown_groups_share_stages_without_hurting_each_other():
+    """16 caller threads, 25 RPCs of 60 requests each, every payload with a group in it (which kind and where changes from RPC to RPC), and a
+    17th caller with plain RPCs of 20, into stages of 128 items: an RPC must reserve the places its items take.  With a host walk that stops
+    at a group each of these RPCs reserves ONE place, a dozen of them share a stage of 128, and the decoder turns whichever crosses the
+    stage's capacity away with GUBER_E_WIRE_TOO_LARGE (-21) — the plain caller's RPCs among them.  No call may fail; every RPC gets exactly
+    its own rows in its requests' order (each caller has keys of its own, token bucket, limit 1000, one hit per RPC: the q-th RPC's rows all
+    say remaining 999 - q); the pool counted every item; and RPCs did share stages."""
+    CALLERS, RPCS, ITEMS, PLAIN_ITEMS, LIMIT = 16, 25, 60, 20, 1000
+    engs = _engines(2, cache_size=1 << 16, max_batch=8192, max_key_bytes=64)
+    place = ga.Placement(2)
+    pool = gw.WirePool(engs, place, stages=3, max_items=128, max_payload_bytes=1 << 20, max_rpcs=64, batch_wait_us=2000, decodes_queued=1)
+    pool.set_clock(NOW)
+    # (payloads are built before the threads start and answers parsed after they have ended: inside the threads there is the call and nothing else)
+    plans = []
+    for t in range(CALLERS + 1):
+        n = ITEMS if t < CALLERS else PLAIN_ITEMS
+        recs = [wire_shapes.record(wire_shapes.req("c%02d_%02d" % (t, j), limit=LIMIT)) for j in range(n)]
+        mine = []
+        for q in range(RPCS):
+            if t == CALLERS:
+                mine.append(b"".join(recs))
+                continue
+            kind = wire_shapes.GROUP_KINDS[(t + q) % len(wire_shapes.GROUP_KINDS)]
+            mine.append(wire_shapes.chain(recs, wire_shapes.ELEMENTS[kind][0], wire_shapes.POSITIONS[(q + t // 2) % 3]))
+        plans.append(mine)
+    raw = [[None] * RPCS for _ in plans]
+    failures = []
+    start = threading.Barrier(len(plans))
+
+    def caller(t):
+        start.wait()
+        for q, payload in enumerate(plans[t]):
+            try:
+                raw[t][q] = pool.get_rate_limits(payload)
+            except Exception as e:  # noqa: BLE001
+                failures.append((t, q, repr(e)))
+
+    th = [threading.Thread(target=caller, args=(t,)) for t in range(len(plans))]
+    for x in th:
+        x.start()
+    for x in th:
+        x.join()
+    assert not failures, ("%d of %d calls failed" % (len(failures), len(plans) * RPCS), failures[:3])
+    for t, mine in enumerate(raw):
+        n = ITEMS if t < CALLERS else PLAIN_ITEMS
+        for q, got in enumerate(mine):
+            rows = wire_replay.rows_of(got)
+            assert len(rows) == n, (t, q, len(rows))
+            assert all(r[:3] == (0, LIMIT, LIMIT - 1 - q) and r[4] == "" for r in rows), (t, q, rows[:3])
+    st = pool.stats()
+    assert st["items"] == CALLERS * RPCS * ITEMS + RPCS * PLAIN_ITEMS
+    assert st["rpcs"] == (CALLERS + 1) * RPCS and st["stages"] < st["rpcs"]          # RPCs shared stages
+    assert sum(e.size() for e in engs) == CALLERS * ITEMS + PLAIN_ITEMS
+    pool.close()
+    for e in reversed(engs):
+        e.close()
+    place.close()

@@ -30,6 +30,8 @@ static LruKeys lru_keys_of(const BatchView& B) {
     LruKeys K{};
     K.bytes = B.key_bytes; K.algorithm = B.algorithm; K.key_stride = B.key_stride;
     K.behavior = B.behavior; K.duration = B.duration; K.greg_duration = (B.greg_expire && B.greg_duration) ? B.greg_duration : nullptr;
+    K.key_width = B.key_width;
+    if (B.key_width) return K;
     if (!B.key_stride) { K.off_p = (const uint8_t*)B.key_off; K.off_stride = 4; }
     if (B.key_stride || B.key_len) { K.len_p = (const uint8_t*)B.key_len; K.len_stride = 4; }
     return K;
@@ -313,7 +315,8 @@ static int launch_batch_inner(guber_engine* e, const BatchView& B, const ResultV
 static BatchView batch_slice(const BatchView& B, uint32_t pos, uint32_t len) {
     BatchView S = B;
     S.n = len;
-    if (B.key_stride) S.key_bytes = B.key_bytes + (size_t)pos * B.key_stride; else S.key_off = B.key_off + pos;
+    if (B.key_width) S.key_bytes = B.key_bytes + (size_t)pos * B.key_width;
+    else if (B.key_stride) S.key_bytes = B.key_bytes + (size_t)pos * B.key_stride; else S.key_off = B.key_off + pos;
     if (B.key_len) S.key_len = B.key_len + pos;
     S.hits = B.hits + pos; S.limit = B.limit + pos; S.duration = B.duration + pos;
     if (B.burst) S.burst = B.burst + pos;

@@ -754,7 +754,7 @@ extern "C" int guber_stage_submit_routed(guber_stage_t* s, guber_engine_t* const
         if (!nj) continue;
         guber_engine* e = engines[j];
         BatchView B{nj, 0, d_keys, A.d_key_off + base, A.d_hits + base, A.d_limit + base, A.d_duration + base, A.d_burst + base, A.d_created_at + base,
-                    A.d_algorithm + base, A.d_behavior + base, A.d_is_owner + base, nullptr, nullptr, b.now_ms, 0, A.d_key_len + base};
+                    A.d_algorithm + base, A.d_behavior + base, A.d_is_owner + base, nullptr, nullptr, b.now_ms, 0, 0, A.d_key_len + base};
         ResultView R{o_status + base, o_limit + base, o_remaining + base, o_reset + base, o_err + base};
         if (exact) { xe[nx] = e; XB[nx] = B; XR[nx] = R; ++nx; }
         else { const int rc = pg.add(e, B, R, false); if (rc) return rc; }   // (nothing has been launched; the stage stays idle)

@@ -764,6 +764,34 @@ GB_HD uint64_t xxhash64_words4(const uint64_t w[4], uint32_t len, uint64_t seed)
     return h;
 }
 
+// xxhash64_words4 for a length the caller knows to be the SAME in every lane that calls it (a batch of fixed-width keys: the width the
+// speculative key fetch guessed, confirmed for this lane).  Every branch is on `len` alone, so on the device a wave takes one way through
+// and executes only the rounds the width has — len >> 3 word rounds, the 4-byte round if len & 4, len & 3 byte rounds — where the generic
+// form predicates three word rounds, the 4-byte round and three byte rounds on a per-lane length.  Words behind the one holding the
+// key's last byte are not read (w[k] for 8 k >= len may be anything), nor are that word's bytes behind the key.
+GB_HD uint64_t xxhash64_words4_uniform(const uint64_t w[4], uint32_t len, uint64_t seed) {
+    using namespace xxh;
+    uint64_t h = seed + P5 + (uint64_t)len;
+    uint64_t t;
+    switch (len >> 3) {
+    case 0: t = w[0]; break;
+    case 1: h ^= round1(0, w[0]); h = rotl(h, 27) * P1 + P4; t = w[1]; break;
+    case 2: h ^= round1(0, w[0]); h = rotl(h, 27) * P1 + P4; h ^= round1(0, w[1]); h = rotl(h, 27) * P1 + P4; t = w[2]; break;
+    default:
+        h ^= round1(0, w[0]); h = rotl(h, 27) * P1 + P4; h ^= round1(0, w[1]); h = rotl(h, 27) * P1 + P4;
+        h ^= round1(0, w[2]); h = rotl(h, 27) * P1 + P4; t = w[3]; break;
+    }
+    if (len & 4u) { h ^= (uint64_t)(uint32_t)t * P1; h = rotl(h, 23) * P2 + P3; t >>= 32; }
+    switch (len & 3u) {
+    case 3: h ^= (t & 0xffull) * P5; h = rotl(h, 11) * P1; t >>= 8; [[fallthrough]];
+    case 2: h ^= (t & 0xffull) * P5; h = rotl(h, 11) * P1; t >>= 8; [[fallthrough]];
+    case 1: h ^= (t & 0xffull) * P5; h = rotl(h, 11) * P1; break;
+    default: break;
+    }
+    h ^= h >> 33; h *= P2; h ^= h >> 29; h *= P3; h ^= h >> 32;
+    return h;
+}
+
 // FNV-1 / FNV-1a 64 (segmentio/fasthash v1.0.2; replicated_hash.go:33, config.go:429-433)
 GB_HD uint64_t fnv1_64(const uint8_t* p, uint32_t len) {
     uint64_t h = 0xcbf29ce484222325ULL;

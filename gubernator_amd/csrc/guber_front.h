@@ -33,6 +33,9 @@ struct guber_front {
     // streams of its own (answers, a second routing stream: GUBER_FRONT_STREAMS=2|3 in the laboratory build) lose 5 - 10 %: the HIP
     // runtime maps streams onto four hardware queues, a fifth stream shares one (and GPU_MAX_HW_QUEUES=8 halves the rate).
     const guber::WireEnc* enc_hook = nullptr;         // set around a front_eval call by the payload stage: k_wire_enc in k_fr_out's place (front_out)
+    // fwd[] (arrival position -> place in the shares) has ONE reader, k_wire_enc: k_fr_scatter writes it only for a front whose answers
+    // go through the encoder.  The payload stage says so before it routes anything through the front (guber_wire_dev.h); never cleared.
+    std::atomic<bool> want_fwd{false};
     hipStream_t rs = nullptr, rs2 = nullptr, os = nullptr, last_os = nullptr; int n_own_streams = 1; bool out_on_eval = false; uint32_t out_delay = 0, one_pair_max = FRONT_ONE_PAIR_MAX; bool rs_borrowed = false;
     uint32_t cap = 0, depth = 0, max_key = 0;
     uint32_t seq = 0;
@@ -40,6 +43,7 @@ struct guber_front {
     struct Slot {
         DevBuf<uint8_t> mem; CohBuf<FrontHost> host;
         FrIn in{};
+        uint32_t* fwd = nullptr;                        // the mirror's fwd column (FrIn::d_fwd of a generation routed with want_fwd)
         uint8_t *o_status = nullptr, *o_err = nullptr; int64_t *o_limit = nullptr, *o_remaining = nullptr, *o_reset = nullptr;
         hipEvent_t ev_in = nullptr, ev_out = nullptr, ev_a = nullptr; bool out_recorded = false;
         std::vector<std::unique_ptr<EvalHook>> hooks;   // one per engine stream
@@ -162,7 +166,7 @@ extern "C" int guber_front_create(guber_engine_t* const* engines, uint32_t n_eng
         if (f->streams.size() == 1 && n_engines > 1 && (s.h_margs.ensure(sizeof(MultiArgsMem)) || s.d_margs.ensure(sizeof(MultiArgsMem)))) return GUBER_E_NOMEM;
         uint8_t* p = s.mem.p;
         FrIn& A = s.in;
-        A.d_key_off = (uint32_t*)p; p += front_col(cap * 4 + 4); A.d_key_len = (uint32_t*)p; p += front_col(cap * 4 + 4); A.d_fwd = (uint32_t*)p; p += front_col(cap * 4 + 4);
+        A.d_key_off = (uint32_t*)p; p += front_col(cap * 4 + 4); A.d_key_len = (uint32_t*)p; p += front_col(cap * 4 + 4); s.fwd = (uint32_t*)p; p += front_col(cap * 4 + 4);
         A.d_hits = (int64_t*)p; p += front_col(cap * 8); A.d_limit = (int64_t*)p; p += front_col(cap * 8); A.d_duration = (int64_t*)p; p += front_col(cap * 8);
         A.d_burst = (int64_t*)p; p += front_col(cap * 8); A.d_created_at = (int64_t*)p; p += front_col(cap * 8);
         A.d_behavior = (uint32_t*)p; p += front_col(cap * 4); A.d_algorithm = p; p += front_col(cap); A.d_is_owner = p; p += front_col(cap);
@@ -224,6 +228,7 @@ static int front_route(guber_front* f, guber_front::Slot& s, const FrontGen* fg,
     A.key_bytes = b->key_bytes; A.key_off = b->key_off; A.key_stride = fg->key_stride; A.key_len = fg->key_len; A.hits = b->hits; A.limit = b->limit; A.duration = b->duration;
     A.burst = b->burst; A.created_at = b->created_at; A.behavior = b->behavior; A.algorithm = b->algorithm; A.is_owner = b->is_owner;
     A.R = f->rule;
+    A.d_fwd = f->want_fwd.load(std::memory_order_relaxed) ? s.fwd : nullptr;
     const uint32_t tiles = (b->n + FR_TILE - 1u) / FR_TILE;
     guber_engine* e0 = f->eng[0];
     std::unique_lock<std::mutex> pl(e0->mu, std::defer_lock);       // (the per-kernel timing's spans and events belong to the first engine)
@@ -267,6 +272,7 @@ static int front_out(guber_front* f, guber_front::Slot& s, guber_result_t* r) {
         hipLaunchKernelGGL(k_fr_out_store, dim3((s.n + FR_TILE - 1u) / FR_TILE), dim3(256), 0, os, S);
     } else if (f->enc_hook) {
         // the payload stage (guber_wire_pool.h): the answers' last hop is the encoder — every RPC's GetRateLimitsResp bytes from the shares, through fwd
+        if (!s.in.d_fwd) return fail(GUBER_E_INVALID_ARG, "guber_front: the generation was routed without fwd (want_fwd is set before the routing)");
         guber::WireEnc E = *f->enc_hook;
         E.fwd = s.in.d_fwd; E.d_status = O.d_status; E.d_err = O.d_err; E.d_limit = O.d_limit; E.d_remaining = O.d_remaining; E.d_reset = O.d_reset_time;
         hipLaunchKernelGGL(guber::k_wire_enc, dim3(E.nrpc), dim3(guber::WE_T), 0, os, E);
@@ -388,6 +394,8 @@ static int front_eval_locked(guber_front* f, const FrontGen* gens, guber_result_
             uint32_t counts[MULTI_MEM_MAX];
             for (int q = 0; q < MULTI_MEM_MAX; ++q) counts[q] = (uint32_t)s.host.p->w[q];
             const bool packed = !((uint32_t)s.host.p->w[MULTI_MEM_MAX] >> 8 & 1u);
+            const uint32_t width = (uint32_t)s.host.p->w[MULTI_MEM_MAX] & 0xffu;      // (packed: 1 .. FR_KEY_COPY_MAX, k_fr_count has seen to it)
+            if (packed && (width == 0 || width > FR_KEY_COPY_MAX)) { rc = fail(GUBER_E_HIP, "guber_front: a packed generation without a key width"); break; }
             for (auto st : f->streams) { if (hipStreamWaitEvent(st, s.ev_in, 0) != hipSuccess) { rc = fail(GUBER_E_HIP, "hipStreamWaitEvent"); break; } }
             if (rc) break;
             uint32_t base = 0, total = 0;
@@ -406,10 +414,11 @@ static int front_eval_locked(guber_front* f, const FrontGen* gens, guber_result_
                 for (uint32_t pos = 0; pos < nj; pos += piece) {
                     const uint32_t len = std::min(piece, nj - pos), d0 = base + pos;
                     const FrIn& A = s.in;
-                    BatchView B{len, 0, packed ? A.d_keys : b->key_bytes, A.d_key_off + d0, A.d_hits + d0, A.d_limit + d0, A.d_duration + d0,
+                    // (a packed generation's pieces say where their keys are with key_width: k_fr_scatter wrote no offsets for them)
+                    BatchView B{len, 0, packed ? A.d_keys + (size_t)d0 * width : b->key_bytes, packed ? nullptr : A.d_key_off + d0, A.d_hits + d0, A.d_limit + d0, A.d_duration + d0,
                                 b->burst ? A.d_burst + d0 : nullptr, b->created_at ? A.d_created_at + d0 : nullptr,
                                 A.d_algorithm + d0, A.d_behavior + d0, b->is_owner ? A.d_is_owner + d0 : nullptr, nullptr, nullptr, b->now_ms,
-                                0, packed ? nullptr : A.d_key_len + d0};
+                                0, packed ? width : 0u, packed ? nullptr : A.d_key_len + d0};
                     fifo[j].push_back(GroupItem{B, ResultView{s.o_status + d0, s.o_limit + d0, s.o_remaining + d0, s.o_reset + d0, s.o_err + d0},
                                                 f->st.active ? f->st.flags.p + d0 : nullptr, f->st.active ? f->st.after.p + d0 : nullptr});
                 }

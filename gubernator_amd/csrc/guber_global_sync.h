@@ -293,7 +293,7 @@ static int gs_eval_rows(guber_comm* c, GsRank* r, const uint8_t* rows, uint32_t 
     for (uint32_t lo = 0; lo < n; lo += e->max_batch) {
         const uint32_t m = std::min<uint32_t>(e->max_batch, n - lo);
         BatchView B{m, 0, rows + (size_t)lo * rb, nullptr, O.hits + lo, O.limit + lo, O.duration + lo, O.burst + lo, O.created_at + lo,
-                    O.algorithm + lo, O.behavior + lo, is_owner ? nullptr : r->zero8.p, nullptr, nullptr, now_ms, rb, O.key_len + lo};
+                    O.algorithm + lo, O.behavior + lo, is_owner ? nullptr : r->zero8.p, nullptr, nullptr, now_ms, rb, 0, O.key_len + lo};
         ResultView R{r->res8.p + lo, c64 + 5 * (size_t)n + lo, c64 + 6 * (size_t)n + lo, c64 + 7 * (size_t)n + lo, r->res8.p + n + lo};
         const int rc = launch_batch(e, B, R);
         if (rc) return rc;

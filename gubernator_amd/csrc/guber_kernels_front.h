@@ -17,7 +17,8 @@ namespace guber {
 //                 on any batch; fwd[i] = d.  The tile is put into the shares' order in LDS first (the place there is computed:
 //                 lbase[engine] + rank), so consecutive threads store consecutive d of a run.  Keys of ONE width (<= 32 bytes:
 //                 every front end that formats its keys) travel with their requests as 8-byte words through the same LDS —
-//                 share j's keys are packed, key_off[d] = d x width, so k_part's speculative key fetch applies —
+//                 share j's keys are packed, key d at d x width (no offsets are written: BatchView::key_width says it), so k_part's
+//                 speculative key fetch applies without loading any —
 //                 other keys stay where they are and the share carries offset + length (BatchView.key_len)
 //   k_fr_out      the same, mirrored: consecutive threads load consecutive share answers of a run, LDS, answer i from the place
 //                 er[i] gives: coalesced reads in the shares' order, coalesced writes in arrival order (fwd is not read)
@@ -51,7 +52,8 @@ struct FrIn {
     const int64_t *hits, *limit, *duration, *burst, *created_at; const uint32_t* behavior; const uint8_t *algorithm, *is_owner;
     // scratch of the slot
     uint16_t* er; uint32_t* tile_cnt; uint32_t* tile_base; FrontCtl* ctl; FrontHost* host;
-    // the mirror: the shares, engine after engine
+    // the mirror: the shares, engine after engine (d_key_off / d_key_len are written for a ragged generation only — a packed one's pieces carry
+    // BatchView::key_width; d_fwd is null unless the answers' last hop is k_wire_enc, its one reader)
     uint32_t *d_key_off, *d_key_len, *d_fwd; int64_t *d_hits, *d_limit, *d_duration, *d_burst, *d_created_at; uint32_t* d_behavior; uint8_t *d_algorithm, *d_is_owner;
     uint8_t* d_keys;
     RouteRule R;
@@ -78,21 +80,22 @@ __global__ __launch_bounds__(FR_TILE) void k_fr_count(FrIn A) {
     uint32_t e = 0xffu;
     if (i < A.n) {
         // keys of one width: the key's words are requested at the place the first two offsets suggest, together with the request's own
-        // offsets, and used if those confirm the guess (as k_part does: one dependent trip less)
-        // (keys as rows: a row's place is known, its length is the guess; 32 bytes of the row are readable when the rows are that long)
-        const uint32_t len0 = fr_len0(A);
-        const uint32_t o0 = A.key_stride ? 0u : A.key_off[0], oend = A.key_stride ? A.n * A.key_stride : A.key_off[A.n];
+        // offsets, and used if those confirm the guess (key_fetch_spec, guber_table.h, as k_part does: one dependent trip less, and only
+        // the words a key of that width has)
+        // (keys as rows: a row's place is known, its length is the guess; a row is readable to its end, key_stride bytes)
+        const uint32_t len0 = wave_uniform(fr_len0(A));
+        const uint32_t o0 = A.key_stride ? 0u : A.key_off[0], oend = A.key_stride ? 0u : A.key_off[A.n];
         const uint32_t off_g = A.key_stride ? i * A.key_stride : o0 + i * len0;
         uint64_t kw[4] = {0, 0, 0, 0};
-        const bool spec = len0 != 0 && len0 < 32 && (A.key_stride ? A.key_stride >= 32u : (uint64_t)off_g + 32 <= (uint64_t)oend + 8);    // (a packed buffer is readable 8 bytes past the last key)
-        if (spec) { const uint8_t* kp = A.key_bytes + off_g; kw[0] = ld_key_word(kp); kw[1] = ld_key_word(kp + 8); kw[2] = ld_key_word(kp + 16); kw[3] = ld_key_word(kp + 24); }
+        // (a packed buffer is readable 8 bytes past the last key; of a row, its key_stride bytes)
+        const bool spec = key_fetch_spec(A.key_bytes, off_g, len0, A.key_stride ? (uint64_t)off_g + A.key_stride : (uint64_t)oend + 8, kw);
         const uint32_t off = fr_key_off(A, i), len = fr_key_len(A, i, off);
         e = 0;
         // (the hash is not handed on to k_part: a column for it costs the copy kernels 32 B per request, measured -2 % on the routed rate with
         //  k_part hashing less — the pipeline is closer to its transactions than to its instructions: profiles/r06_pass_hash_ab.txt)
         if (A.R.global_engine >= 0 && A.behavior && (A.behavior[i] & 2u)) e = (uint32_t)A.R.global_engine;      // Behavior_GLOBAL: the device's GLOBAL engine
         else if (len != 0 && len <= A.max_key && A.R.n_shards > 1)
-            e = route_engine(A.R, (spec && off == off_g && len == len0) ? xxhash64_words4(kw, len, 0) : xxhash64(A.key_bytes + off, len, 0));
+            e = route_engine(A.R, (spec && off == off_g && len == len0) ? xxhash64_words4_uniform(kw, len0, 0) : xxhash64(A.key_bytes + off, len, 0));
         if (e >= A.n_engines) e = 0;
         if (len != len0 || off != off_g || len0 == 0 || len0 > FR_KEY_COPY_MAX) {
             if (__hip_atomic_load(&A.ctl->ragged_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != A.seq) atomicExch(&A.ctl->ragged_seq, A.seq);
@@ -226,7 +229,7 @@ __global__ __launch_bounds__(256) void k_fr_scatter(FrIn A) {
         const uint32_t e = er >> FR_RANK_BITS;
         p[k] = T.lbase[e] + (er & ((1u << FR_RANK_BITS) - 1u));
         const uint32_t d = T.dofs[e] + p[k];
-        A.d_fwd[i] = d < A.n ? d : 0u;                               // (arrival order: the payload stage's k_wire_enc reads it)
+        if (A.d_fwd) A.d_fwd[i] = d < A.n ? d : 0u;                  // (arrival order; only the payload stage's k_wire_enc reads it: null for every other front)
     }
     uint32_t dd[FR_PER];
     fr_sorted_places(T, A.n, dd);
@@ -285,12 +288,7 @@ __global__ __launch_bounds__(256) void k_fr_scatter(FrIn A) {
                 else for (uint32_t q = 0; q < len0; ++q) dst[q] = (uint8_t)(o[k] >> (8 * q));
             }
         }
-#pragma unroll
-        for (int k = 0; k < FR_PER; ++k) {
-            if (dd[k] == 0xffffffffu) continue;
-            A.d_key_off[dd[k]] = dd[k] * len0;
-            if (dd[k] == A.n - 1) A.d_key_off[A.n] = A.n * len0;
-        }
+        // (no offsets: key d of the mirror is d x len0, which the shares' views say with BatchView::key_width — guber_front.h)
     } else {
         // other keys stay where they are: offset and length travel
         uint64_t ol[FR_PER];

@@ -68,6 +68,7 @@ struct LruKeys {
     const uint8_t* off_p; uint32_t off_stride;     // u32 offset of key i at off_p + i * off_stride (null: i * key_stride)
     const uint8_t* len_p; uint32_t len_stride;     // u32 length likewise (null: off[i + 1] - off[i])
     uint32_t key_stride;
+    uint32_t key_width;                            // != 0: keys of one width, packed (BatchView::key_width): key i at i * key_width, off_p / len_p not read
     const uint8_t* algorithm;                      // requests only: an invalid algorithm never reaches the cache (workers.go:317-321)
     // requests only: DURATION_IS_GREGORIAN with a duration that is no interval constant fails in tokenBucketNewItem / leakyBucketNewItem
     // BEFORE c.Add (algorithms.go; interval.go:93,107,125,148): for a key that is not in the cache such a request is a GetItem miss and
@@ -112,8 +113,8 @@ __global__ __launch_bounds__(256) void k_lru_probe(Table T, LruKeys K, uint32_t 
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     if (K.algorithm && K.algorithm[i] > ALGO_LEAKY) return;
-    const uint32_t off = K.off_p ? lru_u32(K.off_p, K.off_stride, i) : i * K.key_stride;
-    const uint32_t len = K.len_p ? lru_u32(K.len_p, K.len_stride, i) : lru_u32(K.off_p, K.off_stride, i + 1) - off;
+    const uint32_t off = K.key_width ? i * K.key_width : K.off_p ? lru_u32(K.off_p, K.off_stride, i) : i * K.key_stride;
+    const uint32_t len = K.key_width ? K.key_width : K.len_p ? lru_u32(K.len_p, K.len_stride, i) : lru_u32(K.off_p, K.off_stride, i + 1) - off;
     if (len == 0 || len > T.max_key) return;
     const uint8_t* key = K.bytes + off;
     const uint64_t h = xxhash64(key, len, 0);

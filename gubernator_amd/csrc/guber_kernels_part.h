@@ -169,14 +169,13 @@ __device__ __forceinline__ void part_body(const Table& T, const BatchView& B, co
     if (valid) {
         uint32_t off_g = 0, len_g = 0;
         bool spec = false;
-        if (!B.key_stride && !B.key_len && B.n >= 2) {
+        if (B.key_width) {                                           // (a view of one width: the width is the guess, no offsets are loaded)
+            len_g = B.key_width; off_g = g * len_g;
+            spec = key_fetch_spec(B.key_bytes, off_g, len_g, (uint64_t)B.n * len_g + 8, kw);
+        } else if (!B.key_stride && !B.key_len && B.n >= 2) {
             const uint32_t o0 = B.key_off[0], o1 = B.key_off[1], oend = B.key_off[B.n];
-            len_g = o1 - o0; off_g = o0 + g * len_g;
-            if (len_g != 0 && len_g < 32 && (uint64_t)off_g + 32 <= (uint64_t)oend + 8) {   // (the buffer is padded by 8 bytes)
-                spec = true;
-                const uint8_t* kp = B.key_bytes + off_g;
-                kw[0] = ld_key_word(kp); kw[1] = ld_key_word(kp + 8); kw[2] = ld_key_word(kp + 16); kw[3] = ld_key_word(kp + 24);
-            }
+            len_g = wave_uniform(o1 - o0); off_g = o0 + g * len_g;
+            spec = key_fetch_spec(B.key_bytes, off_g, len_g, (uint64_t)oend + 8, kw);      // (the buffer is padded by 8 bytes)
         }
         mine = load_req_nogreg(B, g);
         off = key_off_of(B, g);
@@ -189,7 +188,7 @@ __device__ __forceinline__ void part_body(const Table& T, const BatchView& B, co
                 spec = false;
                 if (len <= 16) { kw[0] = ld_key_word(key); kw[1] = len > 8 ? ld_key_word(key + 8) : 0ull; }
             }
-            h = (spec ? xxhash64_words4(kw, len, 0) : xxhash64(key, len, 0)) & T.hash_mask;
+            h = (spec ? xxhash64_words4_uniform(kw, len_g, 0) : xxhash64(key, len, 0)) & T.hash_mask;
             gk = h ? h : 1ull;
         }
     }

@@ -72,7 +72,9 @@ struct BatchView {
     // keys as rows of a matrix instead of a packed buffer (the GLOBAL exchange evaluates received rows in place):
     // key i = key_bytes + i * key_stride, key_len[i] bytes.  0 = packed, key_off[] applies — with key_len[] as well when the
     // requests are not in the order of their keys (a stage routed to several engines: guber_stage_submit_routed).
-    uint32_t key_stride; const uint32_t* key_len;
+    // key_width != 0: keys of ONE width, packed — key i = key_bytes + i * key_width, key_width bytes (the pieces of a packed generation's
+    // shares: guber_front.h).  key_off and key_len are not read and may be null; every reader goes through key_off_of / key_len_of.
+    uint32_t key_stride; uint32_t key_width; const uint32_t* key_len;
 };
 struct ResultView { uint8_t* status; int64_t *limit, *remaining, *reset_time; uint8_t* err; };
 
@@ -204,9 +206,39 @@ __device__ __forceinline__ uint64_t tail_mask(uint32_t nbytes) {  // nbytes in 1
     return nbytes >= 8 ? ~0ull : ((1ull << (8 * nbytes)) - 1ull);
 }
 
-__device__ __forceinline__ uint32_t key_off_of(const BatchView& B, uint32_t i) { return B.key_stride ? i * B.key_stride : B.key_off[i]; }
+
+// ---- the speculative key fetch of the kernels that hash a batch's keys (k_front, k_part, k_fr_count) ---------------------------------------
+// A value every lane of the wave holds alike (loaded from one address: the batch's first offsets), as a scalar: what depends on it alone
+// is then a scalar branch — the wave executes ONE variant — instead of predicated code for all of them.
+__device__ __forceinline__ uint32_t wave_uniform(uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+#else
+    return v;
+#endif
+}
+// Keys of one width (every front end that formats its keys): the key's words are requested where the batch's guessed width says the key
+// lies — `off_g` — together with the request's own offsets instead of behind them (one dependent trip less); the caller uses them only
+// if the offsets confirm the guess.  len_g is wave-uniform (wave_uniform above).  Only the words the key has are requested,
+// ceil(len_g / 8), with the widest loads that express that: 8 bytes up to width 8, 16 for 9-16, 16 + 8 for 17-24, 32 for 25-31 — for a
+// 16-byte key ONE global_load_dwordx4 at any byte alignment (the key is at g x width: odd for odd widths) where four 8-byte loads went
+// out, two of them for the neighbours' keys.  Nothing is read further behind the key's start than 8 x ceil(len_g / 8) bytes, and nothing
+// at or behind `readable_end` (a packed buffer: its last key's end + the 8 bytes the API promises behind it, so the buffer's last keys take
+// this path too; rows: the row's end).  false: nothing was requested (no guess, a key of 32 bytes or more, or a guess that leads outside).
+__device__ __forceinline__ bool key_fetch_spec(const uint8_t* key_bytes, uint64_t off_g, uint32_t len_g, uint64_t readable_end, uint64_t (&kw)[4]) {
+    const uint32_t nb = (len_g + 7u) & ~7u;
+    if (len_g == 0 || len_g >= 32 || off_g + nb > readable_end) return false;
+    const uint8_t* kp = key_bytes + off_g;
+    if (len_g <= 8) __builtin_memcpy(&kw[0], kp, 8);
+    else if (len_g <= 16) __builtin_memcpy(&kw[0], kp, 16);
+    else if (len_g <= 24) { __builtin_memcpy(&kw[0], kp, 16); __builtin_memcpy(&kw[2], kp + 16, 8); }
+    else __builtin_memcpy(&kw[0], kp, 32);
+    return true;
+}
+
+__device__ __forceinline__ uint32_t key_off_of(const BatchView& B, uint32_t i) { return B.key_width ? i * B.key_width : B.key_stride ? i * B.key_stride : B.key_off[i]; }
 __device__ __forceinline__ uint32_t key_len_of(const BatchView& B, uint32_t i, uint32_t off) {
-    return (B.key_stride || B.key_len) ? B.key_len[i] : B.key_off[i + 1] - off;
+    return B.key_width ? B.key_width : (B.key_stride || B.key_len) ? B.key_len[i] : B.key_off[i + 1] - off;
 }
 __device__ __forceinline__ Req load_req(const BatchView& B, uint32_t i) {
     Req r;

@@ -407,6 +407,7 @@ extern "C" int guber_wire_dev_route_front_async(guber_wire_dev_t* d, guber_front
     if (d->n_items > f->cap) return fail(GUBER_E_BATCH_TOO_LARGE, "more items than the front's generations hold");
     FrontGen g;
     wire_dev_front_gen(d, g);
+    f->want_fwd.store(true, std::memory_order_relaxed);              // (the payload stage's encoder may be this generation's last hop: it reads fwd)
     const int rc = front_route_ahead(f, &g);
     if (!rc) d->routed = true;
     return rc;
@@ -464,6 +465,7 @@ static int wire_dev_eval_front_enc_async(guber_wire_dev* d, guber_front* f, uint
     E.nrpc = d->nrpc; E.first = d->sc.first; E.count = d->sc.count; E.status = d->sc.status;
     E.enc = enc; E.enc_len = enc_len;
     E.h_status = raw->status; E.h_err = raw->err; E.h_limit = raw->limit; E.h_remaining = raw->remaining; E.h_reset = raw->reset_time;
+    f->want_fwd.store(true, std::memory_order_relaxed);              // (before the routing: a generation routed ahead came through guber_wire_dev_route_front_async, which says the same)
     f->enc_hook = &E;
     const int rc = front_eval(f, &g, &dr, 1, nullptr, d->ev_eval);
     f->enc_hook = nullptr;

@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
 FLAG_TEST_WEAK_HASH, FLAG_TEST_FORCE_RADIX, FLAG_TEST_CAREFUL, FLAG_GLOBAL, FLAG_DIR_CLAIMS, FLAG_TEST_NO_SMALL = 1, 2, 4, 8, 16, 32
 FLAG_TEST_FORCE_PART, FLAG_NO_PART = 64, 128
 FLAG_TEST_LATE_COUNTERS = 256    # csrc/guber_test_flags.h: recency stamps, epochs and the snapshot ring's sequence start just below their wraps
+FLAG_TEST_FIXED_ARENA = 512      # csrc/guber_test_flags.h: the long-key arena neither grows nor asks for a rebuild
 
 _lib = None
 

@@ -162,11 +162,12 @@ static int batch_prelude(guber_engine* e, const BatchView& B, Work& W, bool* def
     // (lrucache.go:98-100) and, if the directory is above its load limit, the table rebuilt without its dead entries.  A
     // batch that still finds no room gets per-item GUBER_ITEM_E_TABLE_FULL from the bounded probe, for NEW keys only.
     {
-        const int rc = maintain(e, n, B.now_ms, takes_fast_path(e, n), defer_hard);
+        const uint64_t ab = batch_arena_bytes(e, B);        // (0 for keys that fit their cells: the arena's bound is not looked at)
+        const int rc = maintain(e, n, B.now_ms, takes_fast_path(e, n), defer_hard, ab);
         if (rc) return rc;
         if (defer_hard && *defer_hard) return 0;             // (nothing has been done: the caller comes back)
+        note_enqueued(e, n, ab);
     }
-    note_enqueued(e, n);
     if (++e->epoch >= 0x7fffffffu) {   // 31-bit epoch wrapped: drop all dense-id claims
         hipLaunchKernelGGL(k_clear_claims, dim3((unsigned)((e->slots + 255) / 256)), dim3(256), 0, e->stream, e->T, e->slots);
         e->epoch = 1;
@@ -333,6 +334,9 @@ static BatchView batch_slice(const BatchView& B, uint32_t pos, uint32_t len) {
 // larger than the cache is then evaluated in pieces of cache_size requests, each with its own pre-pass.
 static int launch_batch(guber_engine* e, const BatchView& B, const ResultView& R, bool host_resident = false) {
     if (B.n == 0) return 0;
+    // (a batch the kernels read in place from host memory: its offsets say exactly what its long keys can add to the arena)
+    const bool plain_off = host_resident && !B.key_width && !B.key_stride && !B.key_len && B.key_off;
+    ArenaHint hint(e, plain_off && e->arena_hint == ~0ull ? host_arena_bytes(e, B.key_off, B.n) : ~0ull);
     if (!lru_may_bind(e, B.n)) return launch_batch_inner(e, B, R, host_resident);
     if (B.n > e->max_batch) return fail(GUBER_E_BATCH_TOO_LARGE, "batch larger than guber_config_t.max_batch");
     uint8_t* const sf0 = e->W.store_flags; Rec* const sa0 = e->W.store_after;

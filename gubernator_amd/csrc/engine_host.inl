@@ -6,9 +6,10 @@
 // the same prelude launch_batch has, for the one-launch path
 static int small_prelude(guber_engine* e, const BatchView& B) {
     if (B.now_ms > e->clock_ms) e->clock_ms = B.now_ms;
-    const int rc = maintain(e, B.n, B.now_ms);
+    const uint64_t ab = batch_arena_bytes(e, B);
+    const int rc = maintain(e, B.n, B.now_ms, false, nullptr, ab);
     if (rc) return rc;
-    note_enqueued(e, B.n);
+    note_enqueued(e, B.n, ab);
     take_stamps(e, B.n);
     e->batches++; e->small_batches++;
     return 0;
@@ -52,9 +53,11 @@ static int eval_host_once(guber_engine* e, const guber_batch_t* b, guber_result_
     uint8_t* o8 = base; base += (size_t)n * 2;
     uint8_t* skeys = base;
     uint32_t off = 0;
+    uint64_t long_bytes = 0;                                          // what these keys can add to the long-key arena
     for (uint32_t j = 0; j < n; ++j) {
         const uint32_t i = idx ? idx[j] : j;
         const uint32_t len = b->key_off[i + 1] - b->key_off[i];
+        if (len > INLINE_KEY && len <= e->max_key) long_bytes += (len + 7u) & ~7u;
         memcpy(skeys + off, b->key_bytes + b->key_off[i], len);
         soff[j] = off; off += len;
         s64[j] = b->hits[i]; s64[n + j] = b->limit[i]; s64[2 * (size_t)n + j] = b->duration[i];
@@ -68,6 +71,7 @@ static int eval_host_once(guber_engine* e, const guber_batch_t* b, guber_result_
     }
     soff[n] = off;
     memset(skeys + off, 0, 16);
+    ArenaHint hint(e, long_bytes);
     hipStream_t st = e->stream;
     std::vector<uint8_t> h_sflags; std::vector<Rec> h_safter;
     if (sev) {
@@ -171,8 +175,11 @@ static int eval_batch_host_locked(guber_engine_t* e, const guber_batch_t* b, gub
         rc = eval_host_once(e, b, r, nullptr, b->n, sev);
         if (rc) return rc;
         // two new keys sharing one 64-bit hash inside one batch: re-submit the affected items; on the
-        // second pass the first key is resident and the other one probes past it.
-        for (int round = 0; round < 64; ++round) {
+        // second pass the first key is resident and the other one probes past it.  A round places at least one key of every hash that
+        // still has several and answers the one placed the round before, so n keys under ONE hash (the tests' weak hash) take about
+        // n rounds: the bound follows the batch — a fixed 64 left the rest of such a batch with GUBER_ITEM_E_RETRY, which no caller
+        // is to see.
+        for (uint32_t round = 0; round < 64 + 2 * b->n; ++round) {
             std::vector<uint32_t> again;
             for (uint32_t i = 0; i < b->n; ++i) if (r->err[i] == GUBER_ITEM_E_RETRY) again.push_back(i);
             if (again.empty()) break;

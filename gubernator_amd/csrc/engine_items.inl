@@ -93,10 +93,12 @@ static int add_items_locked(guber_engine_t* e, const guber_item_t* items, uint32
         if (items[i].key_len > e->max_key) return fail(GUBER_E_KEY_TOO_LONG, "item key longer than max_key_bytes");
     }
     {
-        const int rc = maintain(e, n, e->clock_ms);
+        uint64_t ab = 0;
+        if (!e->fixed_arena) for (uint32_t i = 0; i < n; ++i) if (items[i].key_len > INLINE_KEY) ab += (items[i].key_len + 7u) & ~7u;
+        const int rc = maintain(e, n, e->clock_ms, false, nullptr, ab);
         if (rc) return rc;
+        note_enqueued(e, n, ab);
     }
-    note_enqueued(e, n);
     // LRUCache.Add is applied item by item (workers.go:566-581): with duplicates of a key in one call
     // the LAST one must win and the later ones report existed = 1.  Waves of distinct keys keep that; every item carries the
     // recency number of its place in the call, so the order among the call's keys is the reference's too (round 4 numbered the
@@ -183,9 +185,10 @@ extern "C" int guber_move_items_by_hash(guber_engine_t* from, guber_engine_t* to
         hipLaunchKernelGGL(k_items_take_by_hash, dim3((n + 63) / 64), dim3(64), 0, from->stream, from->T, d_h.p, n, stride, from->d_items.p, from->d_ikeys.p);
         if ((he = hipStreamSynchronize(from->stream)) != hipSuccess) break;
         taken = true;
-        rc = maintain(to, n, to->clock_ms);
+        const uint64_t ab = keys_arena_bytes(to, n, std::min(from->max_key, to->max_key));
+        rc = maintain(to, n, to->clock_ms, false, nullptr, ab);
         if (rc) break;
-        note_enqueued(to, n);
+        note_enqueued(to, n, ab);
         hipStream_t st = to->stream;
         hipLaunchKernelGGL(k_items_probe, dim3((n + 255) / 256), dim3(256), 0, st, to->T, from->d_items.p, from->d_ikeys.p, n, to->d_islots.p, to->d_iflags.p);
         hipLaunchKernelGGL(k_items_commit, dim3((n + 255) / 256), dim3(256), 0, st, to->T, from->d_items.p, from->d_ikeys.p, n, to->d_islots.p, to->d_iflags.p,
@@ -405,10 +408,11 @@ extern "C" int guber_add_items_dev(guber_engine_t* e, const guber_items_dev_t* i
     std::lock_guard<std::mutex> lk(e->mu);
     if (e->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
     {
-        const int rc = maintain(e, n, e->clock_ms);
+        const uint64_t ab = keys_arena_bytes(e, n, e->max_key);
+        const int rc = maintain(e, n, e->clock_ms, false, nullptr, ab);
         if (rc) return rc;
+        note_enqueued(e, n, ab);
     }
-    note_enqueued(e, n);
     if (e->d_items.ensure(n) || e->d_islots.ensure(n) || e->d_iflags.ensure(n)) return GUBER_E_NOMEM;
     ItemsSoA S{it->key_off, it->algorithm, it->status, it->limit, it->duration, it->remaining, it->remaining_f, it->stamp, it->burst,
                it->expire_at, it->invalid_at};

@@ -1,8 +1,11 @@
 // engine_maint.inl — part of guber_engine.hip's translation unit (included there, in this order; not a header of its own):
 // maintenance between batches (compaction, eviction, the counters' bounds), per-kernel timing, the time zone.
 // Rebuild the table keeping only live buckets (and buckets with pending GLOBAL work).  Called explicitly (guber_compact) or
-// by maintain() when the directory is above its load limit.
-static int compact_table(guber_engine* e, int64_t now_ms) {
+// by maintain() when the directory is above its load limit or the long-key arena's bound asks for room.
+// arena_room != 0 (maintain, for the arena): the rebuilt arena is to hold its live keys and arena_room more bytes — it is doubled until it
+// does (cells hold OFFSETS into the arena, so the live part is copied as it is).  An allocation that fails leaves the capacity as it was:
+// keys that find no room then get the per-item error.
+static int compact_table(guber_engine* e, int64_t now_ms, uint64_t arena_room) {
     quiesce_all(e);
     DevBuf<DirEntry> ndir; DevBuf<Bucket> nb; DevBuf<uint8_t> narena; DevBuf<GPend> ngp; DevBuf<CompactOut> d_out;
     int rc = ndir.ensure(e->slots) | nb.ensure(e->slots) | narena.ensure(e->T.arena_cap + 64) | d_out.ensure(1);
@@ -27,6 +30,21 @@ static int compact_table(guber_engine* e, int64_t now_ms) {
         cleanup();
         return fail(GUBER_E_HIP, "compaction", he);
     }
+    uint64_t new_cap = e->T.arena_cap;
+    if (arena_room && !e->fixed_arena && co.arena_head <= new_cap) {
+        uint64_t want = new_cap;
+        while (want < co.arena_head + arena_room && want < (1ull << 40)) want *= 2;
+        if (want > new_cap) {
+            DevBuf<uint8_t> grown;
+            if (grown.ensure(want + 64) == 0) {
+                if (co.arena_head == 0 || hipMemcpy(grown.p, narena.p, co.arena_head, hipMemcpyDeviceToDevice) == hipSuccess) {
+                    std::swap(grown.p, narena.p); std::swap(grown.cap, narena.cap);
+                    new_cap = want;
+                }
+            } else (void)hipGetLastError();
+            grown.release();
+        }
+    }
     // tags_used = kept entries; the live count is unchanged except for the expired buckets that were dropped: recount it
     // from the kept entries that are live (kept - pending-but-dead is not tracked separately: size := live kept)
     DevCounters c;
@@ -46,9 +64,9 @@ static int compact_table(guber_engine* e, int64_t now_ms) {
         e->T.gpend = e->gpend.p; e->T.gdirty = e->gdirty.p;
     }
     cleanup();
-    e->T.dir = e->dir.p; e->T.buckets = e->buckets.p; e->T.arena = e->arena.p;
-    e->tags_upper = co.kept; e->size_upper = co.live;
-    e->last_ctr.size = (long long)co.live; e->last_ctr.tags_used = co.kept;
+    e->T.dir = e->dir.p; e->T.buckets = e->buckets.p; e->T.arena = e->arena.p; e->T.arena_cap = new_cap;
+    e->tags_upper = co.kept; e->size_upper = co.live; e->arena_upper = co.arena_head;
+    e->last_ctr.size = (long long)co.live; e->last_ctr.tags_used = co.kept; e->last_ctr.arena_head = co.arena_head;
     rb_disarm_all(e);
     e->lru_tail_ok = false;                                          // the tail list names slots of the old table
     e->compactions++;
@@ -73,7 +91,10 @@ static int evict_to_size(guber_engine* e, int64_t now_ms) {
 // due or a HARD limit (physical room) is at stake.
 // defer_hard (GUBER_FUSE_EP, launch_group): the caller is holding a k_eval3 back on this stream — anything that would enqueue, synchronise
 // or read the counters must wait until that has been launched: *defer_hard = true and NOTHING is done; the caller launches it and calls again
-static int maintain(guber_engine* e, uint64_t incoming, int64_t now_ms, bool batch_follows, bool* defer_hard) {
+// arena_bytes: what the call's long keys can add to the arena (batch_arena_bytes; 0 = none can): the arena's bound is kept like the
+// directory's — near its capacity snapshots ride on the batches, a call that might not fit waits for the exact count and, if it still
+// does not fit, for a rebuild that also grows the arena.  A call without long keys never looks at it.
+static int maintain(guber_engine* e, uint64_t incoming, int64_t now_ms, bool batch_follows, bool* defer_hard, uint64_t arena_bytes) {
     const uint64_t tag_limit = e->slots - e->slots / 8;   // keep >= 1/8 of the entries free
     const uint64_t hard_size = e->cache_size + std::max<uint64_t>(e->cache_size / 2, 4ull * e->max_batch);
     if (e->rb_ride >= 0 && !batch_follows) {              // a snapshot that was to ride on a batch that never came: launch it now
@@ -88,10 +109,12 @@ static int maintain(guber_engine* e, uint64_t incoming, int64_t now_ms, bool bat
     // bound a decision is taken on is the exact count a few batches ago plus what was enqueued since.
     const uint64_t early = std::min<uint64_t>(16 * incoming, e->cache_size / 2);
     const bool over = e->size_upper > e->cache_size, tags = e->tags_upper + incoming > tag_limit;
-    const bool near = e->size_upper + incoming + early > e->cache_size || e->tags_upper + incoming + early > tag_limit;
+    const bool arena = arena_bytes != 0 && e->arena_upper + arena_bytes > e->T.arena_cap;
+    const bool near = e->size_upper + incoming + early > e->cache_size || e->tags_upper + incoming + early > tag_limit ||
+                      (arena_bytes != 0 && e->arena_upper + arena_bytes + std::min<uint64_t>(16 * arena_bytes, e->T.arena_cap / 2) > e->T.arena_cap);
     if (!over && !tags && !near) return 0;
     const bool sure_over = (uint64_t)std::max<long long>(e->last_ctr.size, 0) > e->cache_size && !rb_any_armed(e);
-    const bool hard = (incoming == 0 && (over || tags)) || e->size_upper > hard_size || tags || sure_over;
+    const bool hard = (incoming == 0 && (over || tags)) || e->size_upper > hard_size || tags || arena || sure_over;
     if (!hard) {
         if (batch_follows) (void)rb_arm(e, true);            // no launch of its own: the batch's first kernel carries it
         else if (defer_hard) { *defer_hard = true; return 0; }
@@ -105,9 +128,11 @@ static int maintain(guber_engine* e, uint64_t incoming, int64_t now_ms, bool bat
         rc = evict_to_size(e, now_ms);
         if (rc) return rc;
     }
-    if (e->tags_upper + incoming > tag_limit) {
-        // dead entries (expired, removed, evicted) still hold their tags: rebuild without them
-        rc = compact_table(e, now_ms);
+    const bool arena_now = arena_bytes != 0 && e->arena_upper + arena_bytes > e->T.arena_cap;   // (by the exact count)
+    if (e->tags_upper + incoming > tag_limit || arena_now) {
+        // dead entries (expired, removed, evicted) still hold their tags, and their long keys their place in the arena: rebuild without
+        // them — for the arena with room for this call and for one max_batch of the longest keys
+        rc = compact_table(e, now_ms, arena_now ? std::max<uint64_t>(arena_bytes, keys_arena_bytes(e, e->max_batch, e->max_key)) : 0);
         if (rc) return rc;
     }
     return 0;

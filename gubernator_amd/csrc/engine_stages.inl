@@ -136,6 +136,7 @@ extern "C" int guber_stage_submit(guber_stage_t* s) {
     if (e->small_pending) { const int rcp = resolve_small_locked(e->small_pending, true, e); if (rcp < 0) return rcp; }
     BatchView B = view_of(b);
     const ResultView R = view_of(s->result);
+    ArenaHint hint(e, host_arena_bytes(e, b.key_off, b.n));           // (the stage's offsets are the host's: exact, also when the batch goes to HBM by DMA)
     if (b.n <= FT && !e->no_small && !lru_may_bind(e, b.n)) {
         s->seq = ++e->small_seq ? e->small_seq : ++e->small_seq;
         s->sout->done = 0;
@@ -158,7 +159,7 @@ extern "C" int guber_stage_submit(guber_stage_t* s) {
         e->small_fallbacks++;
     }
     // (maintenance first: it may synchronise and rebuild; the read-back pair must bracket the kernels only)
-    int rc = maintain(e, b.n, b.now_ms);
+    int rc = maintain(e, b.n, b.now_ms, false, nullptr, e->fixed_arena ? 0 : e->arena_hint);
     if (rc) return rc;
     // a batch that fills at least half of the stage reaches HBM by DMA; smaller ones are read in place
     const bool dma = e->stage_dma && s->max_n >= 4096 && (size_t)b.n * 2 >= s->max_n && !b.greg_expire && !b.greg_duration;

@@ -154,6 +154,11 @@ struct guber_engine {
     uint64_t batches = 0;
     uint64_t tags_upper = 0;   // host-side upper bound of ctr.tags_used
     uint64_t size_upper = 0;   // host-side upper bound of the live items (ctr.size)
+    // The long-key arena's bound, kept like tags_upper: arena_upper >= ctr.arena_head, grown per call by the padded bytes its long keys can
+    // add (batch_arena_bytes), tightened by the snapshot folds; maintain() rebuilds — and compact_table grows the arena — before a call
+    // that might not fit.  arena_hint: the exact padded long-key bytes of the host batch being evaluated (~0 = not known).
+    uint64_t arena_upper = 0, arena_added_total = 0, arena_hint = ~0ull;
+    bool fixed_arena = false;  // GUBER_FLAG_TEST_FIXED_ARENA: no bound, no growth
     int64_t clock_ms = 0;      // latest `now` seen (guber_set_clock / batches / lookups): classifies evictions as expired or not
     uint64_t evict_passes = 0;
     // The recency order of LRUCache's list (lrucache.go:88-128) as request sequence numbers: a batch of n requests takes n stamps
@@ -172,7 +177,7 @@ struct guber_engine {
     // a ring of snapshot slots (+ one reserved for the synchronous refresh): every slot remembers how many requests had been
     // enqueued when it was armed, so a completed snapshot gives  exact count as of then + requests enqueued since  as the bound
     static constexpr uint32_t kRb = 32;
-    struct RbSlot { uint32_t seq = 0; uint64_t mark = 0; bool armed = false; };
+    struct RbSlot { uint32_t seq = 0; uint64_t mark = 0, amark = 0; bool armed = false; };
     RbSlot rb[kRb + 1]; int rb_ride = -1;      // rb_ride: the slot that waits for a batch to ride on (k_front / k_part carry it)
     uint64_t added_total = 0;                  // requests (items) ever enqueued: each might have created an item and a directory entry
     uint64_t settle_waits = 0;
@@ -225,7 +230,35 @@ static void quiesce_all(guber_engine* e) { (void)hipStreamSynchronize(e->stream)
 // Snapshots of the device counters travel to device-visible host memory by a small launch of their own (k_ctr_snapshot) or riding
 // on a batch's first kernel (Work::snap_*), each into its own slot with a sequence number stamped when it is complete: no copy
 // engine, no event — the host just looks at the stamps.
-static void note_enqueued(guber_engine* e, uint64_t n) { e->size_upper += n; e->tags_upper += n; e->added_total += n; }
+static void note_enqueued(guber_engine* e, uint64_t n, uint64_t arena_bytes = 0) {
+    e->size_upper += n; e->tags_upper += n; e->added_total += n;
+    e->arena_upper += arena_bytes; e->arena_added_total += arena_bytes;
+}
+// What a call's keys can add to the long-key arena: nothing when no key of it can be longer than a cell holds (the engine's limit, a view
+// of one width, rows); the exact padded bytes where the host has the offsets (arena_hint); otherwise every key at its longest.
+static uint64_t pad8(uint64_t v) { return (v + 7) & ~7ull; }
+static uint64_t keys_arena_bytes(const guber_engine* e, uint64_t n, uint32_t longest) {
+    if (e->fixed_arena || longest <= INLINE_KEY) return 0;
+    return n * pad8(longest);
+}
+// the exact figure from offsets the host can read (n + 1 of them): the padded bytes of the keys above INLINE_KEY
+static uint64_t host_arena_bytes(const guber_engine* e, const uint32_t* off, uint32_t n) {
+    if (e->fixed_arena || e->max_key <= INLINE_KEY || !n || off[n] - off[0] <= INLINE_KEY) return 0;
+    uint64_t s = 0;
+    for (uint32_t i = 0; i < n; ++i) { const uint32_t len = off[i + 1] - off[i]; s += len > INLINE_KEY ? (len + 7u) & ~7u : 0u; }
+    return s;
+}
+// ... held in arena_hint while the batch those offsets belong to is on its way through the preludes (pieces of it count the whole: a bound)
+struct ArenaHint {
+    guber_engine* e; bool mine;
+    ArenaHint(guber_engine* e_, uint64_t bytes) : e(e_), mine(e_->arena_hint == ~0ull) { if (mine) e->arena_hint = bytes; }
+    ~ArenaHint() { if (mine) e->arena_hint = ~0ull; }
+};
+static uint64_t batch_arena_bytes(const guber_engine* e, const BatchView& B) {
+    if (B.key_width) return keys_arena_bytes(e, B.n, std::min(B.key_width, e->max_key));
+    if (e->arena_hint != ~0ull) return e->fixed_arena ? 0 : e->arena_hint;
+    return keys_arena_bytes(e, B.n, B.key_stride ? std::min(B.key_stride, e->max_key) : e->max_key);
+}
 static bool rb_slot_done(const guber_engine* e, uint32_t i) {
     return __atomic_load_n((volatile uint32_t*)&e->h_rb_seq.p[i], __ATOMIC_ACQUIRE) == e->rb[i].seq;
 }
@@ -244,6 +277,7 @@ static void rb_fold_slot(guber_engine* e, uint32_t i) {
     const uint64_t since = e->added_total - e->rb[i].mark;
     e->last_ctr = c;
     e->tags_upper = c.tags_used + since;
+    e->arena_upper = c.arena_head + (e->arena_added_total - e->rb[i].amark);
     e->size_upper = (uint64_t)std::max<long long>(c.size, 0) + since;
 }
 // the newest completed snapshot (if any) becomes the host's knowledge; every completed slot is free again
@@ -268,7 +302,7 @@ static int rb_arm(guber_engine* e, bool ride) {
     for (uint32_t i = 0; i < guber_engine::kRb; ++i) {
         if (e->rb[i].armed) continue;
         e->rb[i].seq = ++e->rb_seq ? e->rb_seq : ++e->rb_seq;
-        e->rb[i].mark = e->added_total; e->rb[i].armed = true;
+        e->rb[i].mark = e->added_total; e->rb[i].amark = e->arena_added_total; e->rb[i].armed = true;
         if (ride) e->rb_ride = (int)i; else rb_launch(e, i);
         return (int)i;
     }
@@ -284,7 +318,7 @@ static void attach_counter_readback(guber_engine* e, Work& W) {
 // the host's knowledge (exact: nothing is in flight) and forgets every older snapshot
 static int enqueue_counter_readback(guber_engine* e) {
     const uint32_t i = guber_engine::kRb;
-    e->rb[i].seq = ++e->rb_seq ? e->rb_seq : ++e->rb_seq; e->rb[i].mark = e->added_total;
+    e->rb[i].seq = ++e->rb_seq ? e->rb_seq : ++e->rb_seq; e->rb[i].mark = e->added_total; e->rb[i].amark = e->arena_added_total;
     rb_launch(e, i);
     HIPCHK(hipGetLastError());
     return 0;
@@ -345,6 +379,7 @@ extern "C" int guber_engine_create(const guber_config_t* cfg, guber_engine_t** o
     e->fast_cap = std::min<uint32_t>(M, FT * FT_MAX_TILES);
     e->force_radix = (cfg->flags & GUBER_FLAG_TEST_FORCE_RADIX) != 0;
     e->always_careful = (cfg->flags & GUBER_FLAG_TEST_CAREFUL) != 0;
+    e->fixed_arena = (cfg->flags & GUBER_FLAG_TEST_FIXED_ARENA) != 0;
     e->no_small = (cfg->flags & (GUBER_FLAG_TEST_NO_SMALL | GUBER_FLAG_TEST_FORCE_PART)) != 0 || e->force_radix || e->always_careful;
     e->zero_copy = guber_lab_env("GUBER_NO_ZEROCOPY") == nullptr;
     e->fuse = guber_lab_env("GUBER_NO_FUSE") == nullptr;
@@ -495,8 +530,8 @@ extern "C" void guber_engine_destroy(guber_engine_t* e) {
 }
 
 // Enqueue the kernel sequence for one batch whose arrays are all in HBM.
-static int compact_table(guber_engine* e, int64_t now_ms);
-static int maintain(guber_engine* e, uint64_t incoming, int64_t now_ms, bool batch_follows = false, bool* defer_hard = nullptr);
+static int compact_table(guber_engine* e, int64_t now_ms, uint64_t arena_room = 0);
+static int maintain(guber_engine* e, uint64_t incoming, int64_t now_ms, bool batch_follows = false, bool* defer_hard = nullptr, uint64_t arena_bytes = 0);
 // What a batch needs before its kernels can be enqueued, shared by the single-engine and the fused multi-engine launch:
 // cache maintenance, the engine's epochs, and (two-launch pipeline) the views / work arrays of this batch.
 struct FastPlan { BatchView B2, B3; Work W; uint32_t ftiles; };

@@ -643,8 +643,11 @@ extern "C" int guber_global_sync(guber_comm_t* c, int64_t now_ms, guber_global_s
         st.items_installed += n; r->last.items_installed = n;
         st.bytes_moved += (uint64_t)n * gs_item_rb(c); r->last.bytes_moved += (uint64_t)n * gs_item_rb(c);
         if (!n) continue;
-        rc = maintain(e, n, now_ms); if (rc) return rc;
-        note_enqueued(e, n);
+        {
+            const uint64_t ab = keys_arena_bytes(e, n, std::min<uint32_t>(c->stride, e->max_key));
+            rc = maintain(e, n, now_ms, false, nullptr, ab); if (rc) return rc;
+            note_enqueued(e, n, ab);
+        }
         if (r->item_in.ensure(n) || r->islots.ensure(n) || r->iflags.ensure(n) || r->ires.ensure(n)) return GUBER_E_NOMEM;
         HIPCHK(hipMemsetAsync(&r->ctr.p->bad, 0, sizeof(unsigned int), e->stream));
         hipLaunchKernelGGL(k_gs_item_in, dim3((n + 255) / 256), dim3(256), 0, e->stream, r->items_recv.p, c->stride, n, r->item_in.p);

@@ -261,8 +261,12 @@ __device__ __forceinline__ void front_body(const Table& T, const BatchView& B, c
                 const uint32_t pr = probe(T, key, len, h, true, cslot);
                 slot = cslot;
                 inserted = (pr & PR_INSERTED) ? 1 : 0;
-                if (pr & PR_FULL) errcode = 6;
-                else { cand = true; rec = T.buckets[cslot].rec; gk = 0x8000000000000000ull | cslot; }
+                if (pr & PR_FULL) {
+                    errcode = 6;
+                    // the request whose key found no room stays in its entry's segment: a request of this launch that met the entry
+                    // before it was marked refused (PR_NEED_VERIFY below) is in that segment and is answered with the segment's error
+                    if (inserted) gk = 0x8000000000000000ull | cslot;
+                } else { cand = true; rec = T.buckets[cslot].rec; gk = 0x8000000000000000ull | cslot; }
             } else {
                 gk = h ? h : 1ull;
             }
@@ -425,7 +429,8 @@ __device__ __forceinline__ void front_body(const Table& T, const BatchView& B, c
             }
             // the claim was issued before this comparison.  A mismatch = a 64-bit hash collision with a resident key:
             // the whole segment is answered RETRY and re-run in careful mode (verify first, claim by slot).
-            if (!eq) my_flags |= SEG_RETRY;
+            // (a refused entry under the key's own tag — guber_table.h cell_refused — is no collision: a long key stays refused)
+            if (!eq) { if (len > INLINE_KEY && (uint32_t)(cell[7] >> 48) == KEY_LEN_REFUSED) errcode = 6; else my_flags |= SEG_RETRY; }
         }
         // an entry that is not READY was inserted during this launch; its key bytes may still be in flight, but every
         // head — the inserter included — has compared its key with the claimer's request, so the key that ends up

@@ -653,7 +653,9 @@ __device__ __forceinline__ void own_body(const Table& T, const BatchView& B, con
                 } else {
                     eq = key_equal(T, slot, lkey, llen);
                 }
-                if (!eq) sf |= SEG_RETRY;                             // a 64-bit hash collision with a resident key: careful round
+                // a 64-bit hash collision with a resident key: careful round — unless the entry is one whose long key found no room
+                // (guber_table.h cell_refused): the key stays refused
+                if (!eq) { if (klen == 31u && llen > INLINE_KEY && cell_refused(T, slot)) { errcode = 6; cand = false; } else sf |= SEG_RETRY; }
             }
             if (fresh || !cand) rec_clear(trec);
             const uint32_t tot = ktot[kid];

@@ -140,7 +140,11 @@ __global__ __launch_bounds__(TILE) void k_scatter(Table T, BatchView B, Work W, 
             const uint32_t slot = W.slot[g];
             if (rf & RF_NEED_VERIFY) {
                 const uint32_t off = key_off_of(B, g);
-                if (!key_equal(T, slot, B.key_bytes + off, key_len_of(B, g, off))) atomicOr(&W.seg_flags[d], SEG_RETRY);
+                const uint32_t len = key_len_of(B, g, off);
+                // (a tentative match with the entry of a long key that found no room — guber_table.h cell_refused — is that key's other
+                // request of this batch, or a key that would be refused in the retry round all the same: refused here)
+                if (!key_equal(T, slot, B.key_bytes + off, len))
+                    atomicOr(&W.seg_flags[d], len > INLINE_KEY && cell_refused(T, slot) ? (SEG_ERR | (6u << 8)) : (uint32_t)SEG_RETRY);
             }
             if (rf & RF_INSERTED) atomicOr(&T.dir[slot].meta, META_READY);
             if (d == g) {

@@ -165,7 +165,8 @@ __device__ __forceinline__ void small_body(const Table& T, const BatchView& B, c
                     }
                 } else eq = key_equal(T, slot, key, len);
             }
-            if (!eq) bail = 1u;
+            // (a refused entry under the key's own tag — guber_table.h cell_refused — is no collision: a long key stays refused)
+            if (!eq) { if (ready && len > INLINE_KEY && (uint32_t)(hc.w[7] >> 48) == KEY_LEN_REFUSED) errcode = 6; else bail = 1u; }
         }
         if (inserted) { atomicOr(&T.dir[slot].meta, META_READY); atomicAdd(&ins_n, 1u); }
         srec[tid] = rec; sslot[tid] = slot; serr[tid] = errcode;

@@ -298,7 +298,15 @@ __device__ __forceinline__ bool key_equal(const Table& T, uint64_t slot, const u
     return true;
 }
 
-// store the key of a freshly claimed slot; false = key arena exhausted
+// A directory entry whose key found no room in the arena ("refused"): the tag stays (tags are write-once), the cell's length is 0xFFFF,
+// which no legal key has, the entry is READY — never tentative — and its bucket stays K_ABSENT: not an item, not counted, no LRU victim,
+// dropped by k_compact.  No request adopts it; a long key that meets it under its own tag is refused (cell_refused) until a rebuild.
+constexpr uint32_t KEY_LEN_REFUSED = 0xffffu;
+__device__ __forceinline__ bool cell_refused(const Table& T, uint64_t slot) {
+    return (uint32_t)(T.buckets[slot].cell.w[7] >> 48) == KEY_LEN_REFUSED;
+}
+
+// store the key of a freshly claimed slot; false = key arena exhausted (the entry is left refused: above)
 __device__ __forceinline__ bool key_store(const Table& T, uint64_t slot, const uint8_t* key, uint32_t len) {
     KeyCell* c = &T.buckets[slot].cell;
     uint64_t w[8];
@@ -320,7 +328,9 @@ __device__ __forceinline__ bool key_store(const Table& T, uint64_t slot, const u
         if (off + need > T.arena_cap) {   // poison the cell: length 0xFFFF never equals a legal key length
 #pragma unroll
             for (int i = 0; i < 7; ++i) c->w[i] = 0;
-            c->w[7] = 0xffffull << 48;
+            c->w[7] = (uint64_t)KEY_LEN_REFUSED << 48;
+            __threadfence();                                   // the cell before the flag
+            atomicOr(&T.dir[slot].meta, META_READY);
             return false;
         }
         for (uint64_t b = 0; b < need; b += 8) {
@@ -364,6 +374,9 @@ __device__ __forceinline__ uint64_t probe_packed(const Table& T, const uint8_t* 
             unsigned long long m = ld_agent(&T.dir[pos].meta);
             if (m & META_READY) {
                 if (key_equal(T, pos, key, len)) return (pos << 32) | PR_FOUND;
+                // a refused entry under this tag: the arena is full until a rebuild, so a long key is refused again without taking
+                // another entry (a short key that merely shares the hash probes on: it needs no arena)
+                if (len > INLINE_KEY && cell_refused(T, pos)) return insert ? ((pos << 32) | PR_FULL) : (uint64_t)PR_MISSING;
             } else {
                 return (pos << 32) | PR_NEED_VERIFY;
             }

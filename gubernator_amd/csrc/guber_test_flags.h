@@ -9,6 +9,7 @@
 #define GUBER_FLAG_TEST_NO_SMALL 32u    /* batches of <= 256 requests take the two-launch pipeline too (not the one-launch small path) */
 #define GUBER_FLAG_TEST_FORCE_PART 64u  /* every batch (also <= 256 requests, also host-resident ones) takes the owner-partitioned three-launch pipeline */
 #define GUBER_FLAG_TEST_LATE_COUNTERS 256u /* the engine's counters start where production is after seconds to days (the values below): nothing else changes */
+#define GUBER_FLAG_TEST_FIXED_ARENA 512u /* the long-key arena keeps its first size: no bound asks for a rebuild, no rebuild grows it — so that a full arena and its per-item refusal can be reached */
 // Where an engine created with GUBER_FLAG_TEST_LATE_COUNTERS starts (guber_engine_create; tests/late_counters.py mirrors the four values and
 // tests/test_late_counters_cpu.py holds the mirror to this file).  The next 4 096 recency stamps have Rec::pad near 0xffffffff and the twenty
 // lower high bits set; stamp 2^52 clears pad, flips every one of those bits and sets bit 52 (Rec::meta bit 31).  A batch takes one epoch and,

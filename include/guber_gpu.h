@@ -71,7 +71,8 @@ extern "C" {
 #define GUBER_ITEM_E_EMPTY_KEY 4u         /* gubernator.go:208-217 (host validation normally catches it) */
 #define GUBER_ITEM_E_RETRY 5u             /* internal: two new keys with one 64-bit hash in one batch; the
                                              host layer re-submits these items, callers never see it */
-#define GUBER_ITEM_E_TABLE_FULL 6u        /* no free directory entry / key arena exhausted */
+#define GUBER_ITEM_E_TABLE_FULL 6u        /* a NEW key found no directory entry within the probe bound, or no room for its bytes (keys above 62 bytes)
+                                             because the key arena could not be grown: "Bounded cache" below */
 #define GUBER_ITEM_E_KEY_TOO_LONG 7u      /* key longer than guber_config_t.max_key_bytes */
 
 typedef struct guber_engine guber_engine_t;
@@ -80,7 +81,7 @@ typedef struct guber_engine guber_engine_t;
 #define GUBER_FLAG_GLOBAL 8u          /* keep per-bucket pending GLOBAL hits / updates (guber_global_take) */
 #define GUBER_FLAG_NO_PART 128u        /* never take the owner-partitioned pipeline: batches of 257 .. 65 536 requests run the
                                           two-launch pipeline with per-batch claims (round 3's; kept as the retry round) */
-/* (bits 1, 2, 4, 32, 64 and 256 select code paths for the test suite — gubernator_amd/csrc/guber_test_flags.h —, bit 16 is accepted and
+/* (bits 1, 2, 4, 32, 64, 256 and 512 select code paths for the test suite — gubernator_amd/csrc/guber_test_flags.h —, bit 16 is accepted and
  *  ignored: a binding passes none of them) */
 
 /* Engine configuration.  Replaces Config.{CacheSize,Workers,CacheFactory}
@@ -452,8 +453,14 @@ int guber_front_store_stats(guber_front_t* f, guber_front_store_stats_t* out);
  *      from one table scan + sort per ~live/(2 x batch) batches: guber_stats_t.tail_rebuilds).
  *      The directory entries of evicted / removed keys are reclaimed by a rebuild of the table (guber_compact,
  *      also automatic when the directory passes 7/8 full; GLOBAL engines included, pending records move with their
- *      buckets; the long-key arena is rebuilt too).  Only when the items themselves cannot be placed do new keys get
- *      GUBER_ITEM_E_TABLE_FULL — per item; resident keys are always served.
+ *      buckets).  Keys above 62 bytes live in an arena that the host bounds as it bounds the directory: per call by the padded
+ *      bytes its long keys can add (exact where the host sees the key lengths, every key at max_key_bytes where only the device
+ *      does), tightened by the counter snapshots; a call that might not fit waits for a rebuild, which drops the dead keys' bytes
+ *      and doubles the arena until the live keys and a max_batch of the longest fit — a cache holds cache_size keys of any legal
+ *      length.  New keys get GUBER_ITEM_E_TABLE_FULL — per item; resident keys are always served — only when the probe bound
+ *      (min(table_slots, 4 096) entries from the key's home) is exhausted or the memory for a larger arena cannot be had.  A key
+ *      refused for the arena stays refused, every request of it, until a rebuild has made room: its directory entry is marked,
+ *      holds no item, counts nowhere and goes with the rebuild.
  *      The engine has no clock: "now" arrives with every batch; maintenance between batches (eviction right after
  *      guber_add_items) classifies items as expired against the latest value seen, which guber_set_clock overrides
  *      (the reference's clock.Freeze / clock.Advance). */

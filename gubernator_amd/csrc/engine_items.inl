@@ -102,7 +102,9 @@ static int add_items_locked(guber_engine_t* e, const guber_item_t* items, uint32
     // LRUCache.Add is applied item by item (workers.go:566-581): with duplicates of a key in one call
     // the LAST one must win and the later ones report existed = 1.  Waves of distinct keys keep that; every item carries the
     // recency number of its place in the call, so the order among the call's keys is the reference's too (round 4 numbered the
-    // items wave by wave: [A, A, D] left A in front of D).
+    // items wave by wave: [A, A, D] left A in front of D).  Waves: new keys that share a 64-bit hash settle one entry per wave — the key that
+    // inserted it is applied in that wave if it has the lowest index at the entry (k_items_probe's vote), in the next wave otherwise —, so m
+    // such keys take at most m + 1 waves; the guard of 64 is far above what real hashes need (GUBER_FLAG_TEST_WEAK_HASH: 64 tags in all).
     const uint64_t stamp0 = take_stamps(e, n);
     std::vector<uint8_t> res(n, 0);
     std::vector<uint32_t> pending(n);

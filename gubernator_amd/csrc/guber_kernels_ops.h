@@ -11,7 +11,9 @@ struct ItemIn {   // device image of guber_item_t with the key referenced by off
     Rec rec; uint32_t key_off, key_len;
 };
 
-// phase A: find-or-insert the directory entry (flags as in k_resolve)
+// phase A: find-or-insert the directory entry (flags as in k_resolve, and IF_ABSENT: found, and the bucket holds no item)
+constexpr uint8_t IF_ABSENT = 8;
+constexpr unsigned long long ITEM_VOTE_META = (K_ABSENT & 3u) | (0xffu << 3);
 __global__ __launch_bounds__(256) void k_items_probe(Table T, const ItemIn* items, const uint8_t* keys, uint32_t n,
                                                      uint32_t* slots, uint8_t* flags) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -25,6 +27,35 @@ __global__ __launch_bounds__(256) void k_items_probe(Table T, const ItemIn* item
         if (pr & PR_FULL) f = RF_ERR;
         if (pr & PR_INSERTED) { f |= RF_INSERTED; atomicAdd(&T.ctr->tags_used, 1ull); }
         if (pr & PR_NEED_VERIFY) f |= RF_NEED_VERIFY;
+        // Items that meet at an entry of THIS launch — the one that inserted it and every tentative match — elect the one with the lowest
+        // index: only that one may be applied by this call's commit (below).  The vote lives in the entry's meta word, which is 0 until the
+        // commit publishes READY: bits 0..31 = ~index, the largest wins; bits 32..62 — the epoch of a batch's claim, never 0 — stay 0.
+        if (!(f & RF_ERR) && (f & (RF_INSERTED | RF_NEED_VERIFY))) {
+            unsigned long long* mp = &T.dir[slot].meta;
+            const unsigned long long vote = 0xffffffffull - i;
+            unsigned long long m = ld_agent(mp);
+            while (!(m & META_READY) && (m & 0xffffffffull) < vote) {
+                const unsigned long long old = atomicCAS(mp, m, vote);
+                if (old == m) break;
+                m = old;
+            }
+        } else if (pr & PR_FOUND) {
+            // The key's entry exists and its bucket holds no item — the key was removed, evicted or moved away and the table has not been
+            // rebuilt since: rows that repeat such a key would likewise all find it absent.  They are rows of ONE key (the probe compared it), so
+            // they vote in the bucket's record, in the word of its meta and recency stamp: meta = ITEM_VOTE_META (kind K_ABSENT under an
+            // algorithm byte no absent record has), the stamp's low word = ~index.  The elected row's commit overwrites the word.
+            unsigned long long* wp = (unsigned long long*)&T.buckets[slot].rec.meta;
+            unsigned long long w = ld_agent(wp);
+            if ((w & 3ull) == K_ABSENT) {
+                f |= IF_ABSENT;
+                const unsigned long long vote = ITEM_VOTE_META | ((0xffffffffull - i) << 32);
+                while ((uint32_t)w != ITEM_VOTE_META || w < vote) {
+                    const unsigned long long old = atomicCAS(wp, w, vote);
+                    if (old == w) break;
+                    w = old;
+                }
+            }
+        }
     }
     slots[i] = slot; flags[i] = f;
 }
@@ -40,13 +71,27 @@ __global__ __launch_bounds__(256) void k_items_commit(Table T, const ItemIn* ite
     if (f & RF_INSERTED) atomicOr(&T.dir[slot].meta, META_READY);
     if (f & RF_ERR) { result[i] = 0xFE; return; }
     if ((f & RF_NEED_VERIFY) && !key_equal(T, slot, keys + items[i].key_off, items[i].key_len)) { result[i] = 0xFF; return; }
-    const bool existed = rec_kind(T.buckets[slot].rec) != K_ABSENT;
+    // an entry of this call: the item the probe elected goes on; every other one — another key under the entry's tag, or the same key once
+    // more: two threads that both found the bucket absent would both count it — comes again (0xFF), the later duplicates of a key behind
+    // its first occurrence, as LRUCache.Add applies them
+    if ((f & (RF_INSERTED | RF_NEED_VERIFY)) && 0xffffffffu - (uint32_t)ld_agent(&T.dir[slot].meta) != i) { result[i] = 0xFF; return; }
+    Rec* dst = &T.buckets[slot].rec;
+    unsigned long long* wp = (unsigned long long*)&dst->meta;
+    if (f & IF_ABSENT) {                                         // the same for the rows of a key whose bucket held no item (the vote: k_items_probe)
+        const unsigned long long w = ld_agent(wp);              // (no longer the vote: the elected row has stored its item already)
+        if ((uint32_t)w != ITEM_VOTE_META || 0xffffffffu - (uint32_t)(w >> 32) != i) { result[i] = 0xFF; return; }
+    }
+    const bool existed = !(f & IF_ABSENT) && rec_kind(*dst) != K_ABSENT;
     Rec nr = items[i].rec;
     // LRUCache.Add pushes / moves the item to the front (lrucache.go:91,96); item i of the call after item i - 1.  ITEMS_KEEP_STAMP: the
     // host has numbered the items itself (guber_add_items applies a call with duplicate keys in several launches: the numbers follow
     // the items' places in the CALL, so the recency order among the call's keys is the reference's whatever the launches were)
     if (touch != ITEMS_KEEP_STAMP) rec_set_stamp(nr, touch + i);
-    T.buckets[slot].rec = nr;
+    // the word of meta and stamp last and in one piece: the rows that lost the vote read it while this one stores
+    dst->limit = nr.limit; dst->duration = nr.duration; dst->remaining = nr.remaining; dst->stamp = nr.stamp; dst->burst = nr.burst;
+    dst->expire_at = nr.expire_at; dst->invalid_at = nr.invalid_at;
+    unsigned long long mw; __builtin_memcpy(&mw, &nr.meta, 8);
+    __hip_atomic_store(wp, mw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (!existed) atomicAdd((unsigned long long*)&T.ctr->size, 1ull);
     result[i] = existed ? 1 : 0;
 }
@@ -72,7 +117,13 @@ __global__ __launch_bounds__(64) void k_items_take_by_hash(Table T, const uint64
         const uint32_t len = (uint32_t)(c->w[7] >> 48);
         if (len == 0 || len > stride || len > T.max_key) break;
         const uint8_t* src = len > INLINE_KEY ? T.arena + c->w[0] : (const uint8_t*)c->w;
+        // a hash that the list names twice: ONE thread takes the bucket — the one that swaps its meta word (kind | recency stamp) for 0;
+        // the other finds it absent, as if it came a launch later (two lanes of one wave would both have read it live)
+        unsigned long long mw; __builtin_memcpy(&mw, &s.meta, 8);
+        if (atomicCAS((unsigned long long*)&T.buckets[pos].rec.meta, mw, 0ull) != mw) break;
         for (uint32_t b = 0; b < len; ++b) keys[(size_t)i * stride + b] = src[b];
+        // (the bytes behind the key, up to the words its readers load: key_store, key_equal and the hash mask the last word's tail, so nothing
+        // depends on them; they are cleared so that a staging row never shows the bytes of an earlier call's key)
         for (uint32_t b = len; b < ((len + 15u) & ~7u) && b < stride; ++b) keys[(size_t)i * stride + b] = 0;
         out.rec = s; out.key_len = len;
         Rec z; rec_clear(z);

@@ -668,7 +668,11 @@ int guber_placement_cancel(guber_placement_t* p, uint64_t key_hash);
 int guber_placement_export(const guber_placement_t* p, struct guber_route_rule* out);
 /* The buckets of the keys with these XXH64 hashes leave `from`'s table and enter `to`'s (two logical shards of ONE GPU), on
  * the device.  The caller guarantees that neither engine has a batch with those keys being formed or in flight.  *moved
- * (optional) = buckets that were live and moved. */
+ * (optional) = buckets that were live and moved.  A hash that names no live bucket is skipped; a hash listed twice moves its bucket once.
+ * A bucket that `to` does not take — its key is longer than `to`'s max_key_bytes, or `to` has no directory entry left for it — is back in
+ * `from` when the call returns, unchanged: the call then returns GUBER_E_TABLE_FULL, with *moved = the buckets that did move, and nothing is
+ * lost.  (A key longer than the staging row — min(max_key_bytes of the two) + 16 bytes, rounded up to a multiple of 8 — is not taken out in
+ * the first place: it stays in `from` and is not reported.)  Moved buckets count against `to`'s cache_size like added items: its next call evicts. */
 int guber_move_items_by_hash(guber_engine_t* from, guber_engine_t* to, const uint64_t* key_hashes, uint32_t n, uint32_t* moved);
 /* The HIP stream the engine enqueues on (hipStream_t), to be handed to guber_config_t.stream of further engines: engines that
  * share device and stream can share launches (guber_stages_submit, guber_eval_batches_routed_dev).  The engine that owns the
@@ -702,7 +706,15 @@ uint32_t guber_ring_points(const guber_ring_t* r, uint64_t* hashes, uint32_t* ow
  *      guber_ring_route_rows_dev  owning peer of every row key (replicated_hash.go:104-119), asynchronous on the engine stream
  *      guber_add_items_dev      LRUCache.Add (lrucache.go:88-103) of device-resident item columns — the receiving side of
  *                               UpdatePeerGlobals (gubernator.go:425-459); keys must be distinct within a call;
- *                               result[i] (device) = 0 / 1 existed, 0xFF resubmit, 0xFE no directory entry; asynchronous */
+ *                               result[i] (device) = 0 / 1 existed, 0xFF resubmit, 0xFE no directory entry; asynchronous.
+ *                               0xFF: the row changed nothing and is to be sent again, the 0xFF rows of a call in their order, in a
+ *                               later call.  It is the answer to every row but the first of a key that the call holds more than once
+ *                               and that held no item before — a key never seen, or one removed, evicted or moved away: the first
+ *                               row is applied (0), a later one sent again finds the key resident (1) and replaces the value, so the
+ *                               last row wins as in LRUCache.Add.  It is also the answer where two new keys of a call share their
+ *                               64-bit hash: then one of the two keys is applied as above and every row of the other reports 0xFF —
+ *                               or, in one call, every row of both.  Rows that repeat a key that DID hold an item (an expired one
+ *                               included) all report 1, and which of their values stays is unspecified: keep those distinct. */
 typedef struct guber_global_rows_dev {
     uint32_t cap; uint32_t key_stride;
     uint8_t* key_bytes; uint32_t* key_len;

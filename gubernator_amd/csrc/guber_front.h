@@ -74,6 +74,39 @@ struct guber_front {
 };
 
 static size_t front_col(size_t bytes) { return (bytes + 63) & ~(size_t)63; }
+// An arena of columns, each starting on a 64-byte line: take<T>(n) is the next one.  A carve from 0 gives the arena's size in `at`.
+struct ColCarver {
+    uintptr_t at;
+    template <class T> T* take(size_t n) { T* p = (T*)at; at += front_col(n * sizeof(T)); return p; }
+};
+// the routing scratch of generations of at most max_n requests (RouteMap, guber_kernels_front.h); `host` is pinned memory of its own
+static RouteMap route_carve(ColCarver& c, size_t max_n, FrontHost* host) {
+    const size_t tiles = (max_n + FR_TILE - 1) / FR_TILE;
+    RouteMap M{};
+    M.er = c.take<uint16_t>(max_n);
+    M.tile_cnt = c.take<uint32_t>(tiles * MULTI_MEM_MAX); M.tile_base = c.take<uint32_t>(tiles * MULTI_MEM_MAX);
+    M.ctl = c.take<FrontCtl>(1); M.host = host;
+    return M;
+}
+// Have all `nwords` words of the routing's report reached host memory?  Every word carries the generation's seq in its upper half
+// (FrontHost): the front waits for 17, the sixteen share sizes and the key-width word, the mesh for 16.
+static bool route_reported(const FrontHost* h, uint32_t nwords, uint32_t seq) {
+    for (uint32_t q = 0; q < nwords; ++q)
+        if ((uint32_t)(__atomic_load_n((volatile const unsigned long long*)&h->w[q], __ATOMIC_ACQUIRE) >> 32) != seq) return false;
+    return true;
+}
+// Spins, then yields, until they have; every 1 024 yields it asks whether the routing's stream has run dry without them: `what` is the error
+static int route_wait_reported(const FrontHost* h, uint32_t nwords, uint32_t seq, int device, hipStream_t st, const char* what) {
+    uint32_t spins = 0;
+    while (!route_reported(h, nwords, seq)) {
+        if (++spins <= 2000) continue;
+        std::this_thread::yield();
+        if ((spins & 0x3ffu) != 0) continue;
+        if (hipSetDevice(device) != hipSuccess) return fail(GUBER_E_HIP, "hipSetDevice");
+        if (hipStreamQuery(st) != hipErrorNotReady && !route_reported(h, nwords, seq)) return fail(GUBER_E_HIP, what);
+    }
+    return 0;
+}
 // a generation as the front's internals see it: the caller's guber_batch_t, or columns whose keys are rows (the device wire decoder's output)
 struct FrontGen { guber_batch_t b; uint32_t key_stride = 0; const uint32_t* key_len = nullptr; };
 
@@ -153,33 +186,31 @@ extern "C" int guber_front_create(guber_engine_t* const* engines, uint32_t n_eng
     if (f->n_own_streams >= 3) HIPCHK(hipStreamCreateWithFlags(&f->rs2, hipStreamNonBlocking));
     if (rule) { const int rc = front_set_rule(f.get(), rule); if (rc) return rc; }
     else f->rule = RouteRule{1, 1, 0, 0, -1, 0, 0, 0, nullptr, nullptr, nullptr};      // one engine: everything is its share
-    const size_t cap = max_n, tiles = (cap + FR_TILE - 1) / FR_TILE;
     f->slots.resize(depth);
     for (auto& s : f->slots) {
+        if (s.host.ensure(1)) return GUBER_E_NOMEM;
+        const size_t cap = max_n, key_bytes = cap * FR_KEY_COPY_MAX + 64;
         // the mirror: request columns, where each request went, the answers in the shares' order, the keys (<= FR_KEY_COPY_MAX bytes each
         // when they travel), then the routing's scratch
-        const size_t bytes = 3 * front_col(cap * 4 + 4) + 5 * front_col(cap * 8) + front_col(cap * 4) + 2 * front_col(cap) +   // requests
-                             3 * front_col(cap * 8) + 2 * front_col(cap) +                                                  // answers
-                             front_col(cap * FR_KEY_COPY_MAX + 64) +                                                         // keys
-                             front_col(cap * 2) + 2 * front_col(tiles * MULTI_MEM_MAX * 4) + front_col(sizeof(FrontCtl));
-        if (s.mem.ensure(bytes) || s.host.ensure(1)) return GUBER_E_NOMEM;
+        auto carve = [&](uint8_t* base) {
+            ColCarver c{(uintptr_t)base};
+            FrIn& A = s.in;
+            A.d_key_off = c.take<uint32_t>(cap + 1); A.d_key_len = c.take<uint32_t>(cap + 1); s.fwd = c.take<uint32_t>(cap + 1);
+            A.d_hits = c.take<int64_t>(cap); A.d_limit = c.take<int64_t>(cap); A.d_duration = c.take<int64_t>(cap);
+            A.d_burst = c.take<int64_t>(cap); A.d_created_at = c.take<int64_t>(cap);
+            A.d_behavior = c.take<uint32_t>(cap); A.d_algorithm = c.take<uint8_t>(cap); A.d_is_owner = c.take<uint8_t>(cap);
+            s.o_limit = c.take<int64_t>(cap); s.o_remaining = c.take<int64_t>(cap); s.o_reset = c.take<int64_t>(cap);
+            s.o_status = c.take<uint8_t>(cap); s.o_err = c.take<uint8_t>(cap);
+            A.d_keys = c.take<uint8_t>(key_bytes);
+            A.M = route_carve(c, cap, s.host.p);
+            return (size_t)(c.at - (uintptr_t)base);
+        };
+        if (s.mem.ensure(carve(nullptr))) return GUBER_E_NOMEM;
+        carve(s.mem.p);
         if (f->streams.size() == 1 && n_engines > 1 && (s.h_margs.ensure(sizeof(MultiArgsMem)) || s.d_margs.ensure(sizeof(MultiArgsMem)))) return GUBER_E_NOMEM;
-        uint8_t* p = s.mem.p;
-        FrIn& A = s.in;
-        A.d_key_off = (uint32_t*)p; p += front_col(cap * 4 + 4); A.d_key_len = (uint32_t*)p; p += front_col(cap * 4 + 4); s.fwd = (uint32_t*)p; p += front_col(cap * 4 + 4);
-        A.d_hits = (int64_t*)p; p += front_col(cap * 8); A.d_limit = (int64_t*)p; p += front_col(cap * 8); A.d_duration = (int64_t*)p; p += front_col(cap * 8);
-        A.d_burst = (int64_t*)p; p += front_col(cap * 8); A.d_created_at = (int64_t*)p; p += front_col(cap * 8);
-        A.d_behavior = (uint32_t*)p; p += front_col(cap * 4); A.d_algorithm = p; p += front_col(cap); A.d_is_owner = p; p += front_col(cap);
-        s.o_limit = (int64_t*)p; p += front_col(cap * 8); s.o_remaining = (int64_t*)p; p += front_col(cap * 8); s.o_reset = (int64_t*)p; p += front_col(cap * 8);
-        s.o_status = p; p += front_col(cap); s.o_err = p; p += front_col(cap);
-        A.d_keys = p; p += front_col(cap * FR_KEY_COPY_MAX + 64);
-        A.er = (uint16_t*)p; p += front_col(cap * 2);
-        A.tile_cnt = (uint32_t*)p; p += front_col(tiles * MULTI_MEM_MAX * 4); A.tile_base = (uint32_t*)p; p += front_col(tiles * MULTI_MEM_MAX * 4);
-        A.ctl = (FrontCtl*)p; p += front_col(sizeof(FrontCtl));
-        A.host = s.host.p;
         memset((void*)s.host.p, 0, sizeof(FrontHost));
-        HIPCHK(hipMemsetAsync(A.ctl, 0, sizeof(FrontCtl), f->rs));
-        HIPCHK(hipMemsetAsync(A.d_keys, 0, front_col(cap * FR_KEY_COPY_MAX + 64), f->rs));   // (the kernels read keys as 8-byte words: the bytes behind the last key are defined)
+        HIPCHK(hipMemsetAsync(s.in.M.ctl, 0, sizeof(FrontCtl), f->rs));
+        HIPCHK(hipMemsetAsync(s.in.d_keys, 0, front_col(key_bytes), f->rs));   // (the kernels read keys as 8-byte words: the bytes behind the last key are defined)
         HIPCHK(hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming));
         for (size_t q = 0; q < f->streams.size(); ++q) {
@@ -259,7 +290,7 @@ static int front_out(guber_front* f, guber_front::Slot& s, guber_result_t* r) {
     f->last_os = os;
     for (auto& h : s.hooks) if (h->st != os) HIPCHK(hipStreamWaitEvent(os, h->ev, 0));
     FrOut O{};
-    O.n = s.n; O.er = s.in.er; O.tile_cnt = s.in.tile_cnt; O.tile_base = s.in.tile_base; O.ctl = s.in.ctl;   // (the slot's routing scratch: routed into again only behind ev_out)
+    O.n = s.n; O.M = s.in.M;                                         // (the slot's routing scratch: routed into again only behind ev_out)
     O.d_status = s.o_status; O.d_err = s.o_err; O.d_limit = s.o_limit; O.d_remaining = s.o_remaining; O.d_reset_time = s.o_reset;
     O.status = r->status; O.err = r->err; O.limit = r->limit; O.remaining = r->remaining; O.reset_time = r->reset_time;
     guber_engine* e0 = f->eng[0];
@@ -268,7 +299,7 @@ static int front_out(guber_front* f, guber_front::Slot& s, guber_result_t* r) {
     e0->span_begin(f->st.active ? KT_FR_OUT_STORE : KT_FR_OUT, s.n, os);
     if (f->st.active) {
         // a store generation: the events travel home with the answers
-        FrOutStore S{O, f->st.flags.p, f->st.after.p, f->st.oflags.p, f->st.oafter.p};
+        FrOutStore S{O, FrOutSide{f->st.flags.p, f->st.after.p, f->st.oflags.p, f->st.oafter.p}};
         hipLaunchKernelGGL(k_fr_out_store, dim3((s.n + FR_TILE - 1u) / FR_TILE), dim3(256), 0, os, S);
     } else if (f->enc_hook) {
         // the payload stage (guber_wire_pool.h): the answers' last hop is the encoder — every RPC's GetRateLimitsResp bytes from the shares, through fwd
@@ -370,24 +401,11 @@ static int front_eval_locked(guber_front* f, const FrontGen* gens, guber_result_
         const guber_batch_t* b = &gens[k].b;
         if (s.n) {
             // the shares' sizes (in pinned memory since k_fr_scan: normally long there)
-            auto reported = [&]() {
-                for (int q = 0; q <= MULTI_MEM_MAX; ++q)
-                    if ((uint32_t)(__atomic_load_n((volatile unsigned long long*)&s.host.p->w[q], __ATOMIC_ACQUIRE) >> 32) != s.seq) return false;
-                return true;
-            };
-            if (!reported()) {
+            if (!route_reported(s.host.p, MULTI_MEM_MAX + 1, s.seq)) {
                 FpSpan sp(&fp[1]);
                 const auto t0 = std::chrono::steady_clock::now();
                 f->host_waits++;
-                uint32_t spins = 0;
-                while (!reported()) {
-                    if (++spins > 2000) {
-                        std::this_thread::yield();
-                        if ((spins & 0x3ffu) == 0 && hipStreamQuery((s.gen & 1) ? f->rs2 : f->rs) != hipErrorNotReady && !reported()) {
-                            rc = fail(GUBER_E_HIP, "guber_front: the routing of a generation did not report"); break;
-                        }
-                    }
-                }
+                rc = route_wait_reported(s.host.p, MULTI_MEM_MAX + 1, s.seq, f->device, (s.gen & 1) ? f->rs2 : f->rs, "guber_front: the routing of a generation did not report");
                 f->host_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
                 if (rc) break;
             }
@@ -489,10 +507,7 @@ static bool front_routed_ahead_ready(guber_front* f) {
     std::lock_guard<std::mutex> lk(f->mu);
     if (!f->pre_routed) return true;
     guber_front::Slot& s = f->slots[f->generations % f->depth];
-    if (s.n == 0) return true;
-    for (int q = 0; q <= MULTI_MEM_MAX; ++q)
-        if ((uint32_t)(__atomic_load_n((volatile unsigned long long*)&s.host.p->w[q], __ATOMIC_ACQUIRE) >> 32) != s.seq) return false;
-    return true;
+    return s.n == 0 || route_reported(s.host.p, MULTI_MEM_MAX + 1, s.seq);
 }
 
 // ---- the Store side channel of a generation routed on the device (include/guber_gpu.h, Config.Store) -------------------------------
@@ -521,7 +536,7 @@ static int front_store_on_host(guber_front* f, guber_front::Slot& s, const Front
     hipLaunchKernelGGL(k_fr_missing, dim3((n + 255u) / 256u), dim3(256), 0, rs, s.in, E);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(miss.data(), E.ask, n, hipMemcpyDeviceToHost, rs));
-    HIPCHK(hipMemcpyAsync(er.data(), s.in.er, (size_t)n * 2, hipMemcpyDeviceToHost, rs));
+    HIPCHK(hipMemcpyAsync(er.data(), s.in.M.er, (size_t)n * 2, hipMemcpyDeviceToHost, rs));
     if (b.behavior) HIPCHK(hipMemcpyAsync(beh.data(), b.behavior, (size_t)n * 4, hipMemcpyDeviceToHost, rs));
     if (g->key_stride) HIPCHK(hipMemcpyAsync(len.data(), g->key_len, (size_t)n * 4, hipMemcpyDeviceToHost, rs));
     else HIPCHK(hipMemcpyAsync(off.data(), b.key_off, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, rs));
@@ -605,7 +620,7 @@ static int front_probe_missing(guber_front* f, const FrontGen* g, guber_front_as
         e0->span_end();
         for (uint32_t w = 0; w < 2; ++w) {
             e0->span_begin(KT_FR_ASK, n, rs);
-            hipLaunchKernelGGL(k_fr_ask, dim3(tiles), dim3(FR_TILE), 0, rs, E, (const uint16_t*)s.in.er, n, w);
+            hipLaunchKernelGGL(k_fr_ask, dim3(tiles), dim3(FR_TILE), 0, rs, E, (const uint16_t*)s.in.M.er, n, w);
             e0->span_end();
         }
         if (hipGetLastError() != hipSuccess) return fail(GUBER_E_HIP, "kernel launch");

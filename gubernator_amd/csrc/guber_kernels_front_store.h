@@ -43,7 +43,7 @@ __device__ __forceinline__ uint32_t fr_store_home(unsigned long long tag) {
 __global__ __launch_bounds__(256) void k_fr_elect(FrIn A, FrStore E) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= A.n) return;
-    const uint32_t e = A.er[i] >> FR_RANK_BITS;
+    const uint32_t e = A.M.er[i] >> FR_RANK_BITS;
     const uint32_t off = fr_key_off(A, i), len = fr_key_len(A, i, off);
     const unsigned long long h = (xxhash64(A.key_bytes + off, len, 0) & E.hash_mask) ^ ((unsigned long long)(e + 1u) << 56);
     const unsigned long long tag = h ? h : 1ull;
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256) void k_fr_elect(FrIn A, FrStore E) {
 
 // request i's key and engine against request q's
 __device__ __forceinline__ bool fr_same_key(const FrIn& A, uint32_t e, const uint8_t* key, uint32_t len, uint32_t q) {
-    if ((uint32_t)(A.er[q] >> FR_RANK_BITS) != e) return false;
+    if ((uint32_t)(A.M.er[q] >> FR_RANK_BITS) != e) return false;
     const uint32_t qoff = fr_key_off(A, q);
     if (fr_key_len(A, q, qoff) != len) return false;
     const uint8_t* other = A.key_bytes + qoff;
@@ -78,7 +78,7 @@ __device__ __forceinline__ bool fr_same_key(const FrIn& A, uint32_t e, const uin
 __global__ __launch_bounds__(256) void k_fr_missing(FrIn A, FrStore E) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= A.n) return;
-    const uint32_t e = A.er[i] >> FR_RANK_BITS;
+    const uint32_t e = A.M.er[i] >> FR_RANK_BITS;
     const uint32_t off = fr_key_off(A, i), len = fr_key_len(A, i, off);
     const uint8_t* key = A.key_bytes + off;
     bool look = E.all != 0u;
@@ -133,66 +133,8 @@ __global__ __launch_bounds__(FR_TILE) void k_fr_ask(FrStore E, const uint16_t* e
 }
 
 // ---- the answers' last hop of a store generation ------------------------------------------------------------------------------
-// What k_fr_out does (the same LDS columns: sorted element j loads from the shares, arrival position i takes it at p(i)), with the side
-// channel: store_flags[d] rides with status and error as one 32-bit column, and the 64-byte Rec store_after[d] — one full sector per
-// request — is loaded by the sorted side (consecutive threads, consecutive d) and stored by the same thread at the request's arrival
-// place, which it learns from a 16-bit column going the other way (arrival position -> LDS at p(i) -> sorted element).  A Rec travels
-// only when its request's GUBER_STORE_ONCHANGE bit is set (nothing else reads it).
-// LDS: the two 8 KB buffers + 4 KB + 2 KB + FrTile.
-struct FrOutStore {
-    FrOut O;
-    const uint8_t* d_flags; const Rec* d_after;                   // the shares' order (Work::store_flags / store_after)
-    uint8_t* flags; Rec* after;                                   // arrival order
-};
-__global__ __launch_bounds__(256) void k_fr_out_store(FrOutStore S) {
-    __shared__ FrTile T;
-    __shared__ uint64_t stg[2][FR_TILE];
-    __shared__ uint32_t sse[FR_TILE];
-    __shared__ uint16_t inv[FR_TILE];
-    const FrOut& A = S.O;
-    const uint32_t tile = blockIdx.x, tid = threadIdx.x, i0 = tile * FR_TILE + tid;
-    fr_tile_bases(T, A.ctl, A.tile_cnt, A.tile_base, tile);
-    uint32_t dd[FR_PER], p[FR_PER], se[FR_PER]; int64_t l[FR_PER], r[FR_PER], t[FR_PER];
-    fr_sorted_places(T, A.n, dd);
-#pragma unroll
-    for (int k = 0; k < FR_PER; ++k) {                               // every load before the first store
-        p[k] = 0xffffffffu;
-        if (i0 + k * 256u < A.n) { const uint32_t er = A.er[i0 + k * 256u]; p[k] = T.lbase[er >> FR_RANK_BITS] + (er & ((1u << FR_RANK_BITS) - 1u)); }
-        if (p[k] >= FR_TILE) p[k] = 0xffffffffu;
-        se[k] = 0; l[k] = r[k] = t[k] = 0;
-        if (dd[k] == 0xffffffffu) continue;
-        const uint32_t err = A.d_err[dd[k]];                          // (a request to be re-submitted carries no events: engine_host.inl does the same)
-        se[k] = (uint32_t)A.d_status[dd[k]] | err << 8 | (err == IE_RETRY ? 0u : (uint32_t)S.d_flags[dd[k]]) << 16;
-        l[k] = A.d_limit[dd[k]]; r[k] = A.d_remaining[dd[k]]; t[k] = A.d_reset_time[dd[k]];
-    }
-#pragma unroll
-    for (int k = 0; k < FR_PER; ++k) {
-        stg[0][tid + k * 256u] = (uint64_t)l[k]; sse[tid + k * 256u] = se[k];
-        if (p[k] != 0xffffffffu) inv[p[k]] = (uint16_t)(tid + k * 256u);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < FR_PER; ++k) {
-        if (p[k] == 0xffffffffu) continue;
-        const uint32_t i = i0 + k * 256u; const uint32_t v = sse[p[k]];
-        A.limit[i] = (int64_t)stg[0][p[k]]; A.status[i] = (uint8_t)v; A.err[i] = (uint8_t)(v >> 8); S.flags[i] = (uint8_t)(v >> 16);
-    }
-#pragma unroll
-    for (int k = 0; k < FR_PER; ++k) {                               // the sorted side: its request's record to the arrival place
-        if (dd[k] == 0xffffffffu || !((se[k] >> 16) & 1u)) continue;
-        const uint32_t i = tile * FR_TILE + inv[tid + k * 256u];
-        if (i < A.n) S.after[i] = S.d_after[dd[k]];
-    }
-#pragma unroll
-    for (int k = 0; k < FR_PER; ++k) stg[1][tid + k * 256u] = (uint64_t)r[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < FR_PER; ++k) if (p[k] != 0xffffffffu) A.remaining[i0 + k * 256u] = (int64_t)stg[1][p[k]];
-#pragma unroll
-    for (int k = 0; k < FR_PER; ++k) stg[0][tid + k * 256u] = (uint64_t)t[k];      // (everybody has passed the second barrier: nobody reads the first column any more)
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < FR_PER; ++k) if (p[k] != 0xffffffffu) A.reset_time[i0 + k * 256u] = (int64_t)stg[0][p[k]];
-}
+// What k_fr_out does, with the side channel: fr_out_tile<true> (guber_kernels_front.h).
+struct FrOutStore { FrOut O; FrOutSide X; };
+__global__ __launch_bounds__(256) void k_fr_out_store(FrOutStore S) { fr_out_tile<true>(S.O, S.X); }
 
 }  // namespace guber

@@ -12,7 +12,7 @@ namespace guber {
 //                destination (stable: arrival order); per tile of 1 024 requests the requests per destination.  GLOBAL requests
 //                (gubernator.go:258-270: never forwarded) and keys the ring cannot place (empty, over-long) have destination self;
 //                own[i] = the is_owner the request is evaluated with
-//   k_mx_scan    k_fr_scan's form: tile bases and the totals per destination, to ctl->tot and — stamped with the call's sequence
+//   k_mx_scan    route_scan: tile bases and the totals per destination, to ctl->tot and — stamped with the call's sequence
 //                number — to pinned memory
 //   k_mx_pack    the tile sorted by destination in LDS (the place is computed: lbase[dest] + rank), one fixed-width record per request
 //                into the send buffer: destination after destination, arrival order inside; consecutive threads write consecutive records
@@ -21,14 +21,19 @@ namespace guber {
 //   k_mx_out     k_fr_out's form: the answer of request i lies at the place its request record had in the send buffer (the answers come
 //                back slice by slice in the order the requests left): sorted element j loads record j (coalesced), arrival position i
 //                takes it from LDS at lbase[dest] + rank (er[i]) and stores in arrival order
-// The front's lessons hold (guber_kernels_front.h): no per-workgroup tickets, no system-scope release at a kernel's end, no scratch.
+// Count, scan, place and report are the front's routing core (guber_kernels_front.h: RouteMap, route_rank_tile, route_scan, fr_place),
+// and its lessons hold: no per-workgroup tickets, no system-scope release at a kernel's end, no scratch.
 // KEYS.  k_mx_count and k_mx_pack are the two kernels that look at a key, and each exists twice: <false> finds request i's key packed
 // (key_bytes + key_off[i], key_off[i + 1] - key_off[i] bytes: what a caller of structure-of-arrays streams holds), <true> finds it in
-// ROWS (key_bytes + i * key_stride, key_len[i] bytes: what the device wire decoder leaves, guber_kernels_wire.h) — k_fr_count's rules
-// for rows: four words of a row are requested ahead only when the rows are 32 bytes apart or more (the guess is key_len[0]), a shorter
-// row's key is hashed from memory, and no byte outside [row, row + key_stride) is read: the padding behind a key is the caller's and
-// need not be zero.  A row cannot hold more than key_stride bytes: a key_len above it is an over-long key.  The form is the
-// instantiation's, not a branch: the packed kernels are what they were before rows existed (profiles/mesh_kernels.txt).
+// ROWS (key_bytes + i * key_stride, key_len[i] bytes: what the device wire decoder leaves, guber_kernels_wire.h).  k_mx_count asks for a
+// key's words ahead of its offsets through key_fetch_spec (guber_table.h), with what k_fr_count passes: the guess is the first key's
+// width — packed, key i at key_off[0] + i x width; rows, at its row's start — and only the words a key of that width has are
+// requested, 8 x ceil(width / 8) bytes, which must end at or before readable_end: 8 bytes behind a packed buffer's last key, the
+// row's end for a row (so rows closer than 32 bytes speculate too, when the guess fits a row).  A guess of 0 or of 32 bytes and more,
+// or one the request's own offset and length do not confirm, leaves the key to be hashed from memory, its own bytes alone.  So no byte
+// outside [row, row + key_stride) is read — the padding behind a key is the caller's and need not be zero — and nothing at or past 8
+// bytes behind a packed buffer's last key.  A row cannot hold more than key_stride bytes: a key_len above it is an over-long key.
+// The form is the instantiation's, not a branch (profiles/mesh_kernels.txt).
 // (dest[i], place[i]) of a request are er[i] and the tile's bases, as in the front: 2 bytes per request instead of 8.
 //
 // A request record: 64 bytes of columns, then the key row —
@@ -46,7 +51,7 @@ struct MxIn {
     const int64_t *hits, *limit, *duration, *burst, *created_at; const uint32_t* behavior; const uint8_t* algorithm;
     int64_t now_ms;
     const uint64_t* ring_hash; const uint8_t* ring_owner;          // the ring's sorted points (replicated_hash.go:90) and their peers
-    uint16_t* er; uint8_t* own; uint32_t* tile_cnt; uint32_t* tile_base; FrontCtl* ctl; FrontHost* host;
+    RouteMap M; uint8_t* own;
     uint8_t* send; uint32_t rec_bytes;
     uint32_t key_stride; const uint32_t* key_len;                   // <true> only: the rows' distance (a multiple of 8) and the keys' lengths
 };
@@ -66,37 +71,29 @@ __device__ __forceinline__ uint64_t mx_fnv_words4(const uint64_t (&w)[4], uint32
 }
 
 template <bool ROWS> __global__ __launch_bounds__(FR_TILE) void k_mx_count(MxIn A) {
-    GUBER_DYN_LDS(smem);                                             // the ring's hashes (npts x 8 bytes) when they fit beside wtot
-    __shared__ uint32_t wtot[FR_TILE / 64][MULTI_MEM_MAX];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, i = blockIdx.x * FR_TILE + tid;
+    GUBER_DYN_LDS(smem);                                             // the ring's hashes (npts x 8 bytes) when they fit beside route_rank_tile's 1 KB
+    const uint32_t tid = threadIdx.x, i = blockIdx.x * FR_TILE + tid;
     const uint64_t* lh = A.ring_hash;
     if (A.ring_lds) {
         uint64_t* l = (uint64_t*)smem;
         for (uint32_t j = tid; j < A.npts; j += FR_TILE) l[j] = A.ring_hash[j];
         lh = l;
+        __syncthreads();
     }
-    if (tid < (FR_TILE / 64) * MULTI_MEM_MAX) (&wtot[0][0])[tid] = 0u;
-    __syncthreads();
     uint32_t e = 0xffu;
     if (i < A.n) {
-        // keys of one width: the key's words are requested where the first two offsets suggest, together with the request's own offsets,
-        // and used if those confirm the guess (k_fr_count's way: one dependent trip less)
-        // (rows: a row's place is known, key_len[0] is the guess, and 32 bytes of a row are readable only when the rows are that far apart)
-        uint32_t len0, off_g, off, len; bool spec;
+        // keys of one width: the key's words are requested where the first key's width suggests, together with the request's own offsets,
+        // and used if those confirm the guess (key_fetch_spec; KEYS above)
+        uint32_t off, len; uint64_t off_g, readable_end;
+        const uint32_t len0 = wave_uniform(ROWS ? A.key_len[0] : A.key_off[1] - A.key_off[0]);
+        if constexpr (ROWS) { off_g = (uint64_t)i * A.key_stride; readable_end = off_g + A.key_stride; }
+        else { off_g = (uint64_t)A.key_off[0] + (uint64_t)i * len0; readable_end = (uint64_t)A.key_off[A.n] + 8; }
         uint64_t kw[4] = {0, 0, 0, 0};
+        const bool spec = key_fetch_spec(A.key_bytes, off_g, len0, readable_end, kw);
         if constexpr (ROWS) {
-            len0 = A.key_len[0]; off_g = i * A.key_stride;
-            spec = len0 != 0 && len0 < 32 && A.key_stride >= 32u;
-            if (spec) { const uint8_t* kp = A.key_bytes + off_g; kw[0] = ld_key_word(kp); kw[1] = ld_key_word(kp + 8); kw[2] = ld_key_word(kp + 16); kw[3] = ld_key_word(kp + 24); }
-            off = off_g; len = A.key_len[i];
+            off = (uint32_t)off_g; len = A.key_len[i];
             if (len > A.key_stride) len = A.max_key + 1u;            // (more than a row holds: over-long, never read)
-        } else {
-            const uint32_t o0 = A.key_off[0], oend = A.key_off[A.n];
-            len0 = A.key_off[1] - o0; off_g = o0 + i * len0;
-            spec = len0 != 0 && len0 < 32 && (uint64_t)o0 + (uint64_t)i * len0 + 32 <= (uint64_t)oend + 8;   // (a packed buffer is readable 8 bytes past the last key)
-            if (spec) { const uint8_t* kp = A.key_bytes + off_g; kw[0] = ld_key_word(kp); kw[1] = ld_key_word(kp + 8); kw[2] = ld_key_word(kp + 16); kw[3] = ld_key_word(kp + 24); }
-            off = A.key_off[i]; len = A.key_off[i + 1] - off;
-        }
+        } else { off = A.key_off[i]; len = A.key_off[i + 1] - off; }
         const bool stay = (A.behavior && (A.behavior[i] & 2u)) || len == 0 || len > A.max_key;
         // ReplicatedConsistentHash.Get (replicated_hash.go:104-119): the first point at or behind the key's hash, wrapping to point 0
         // (an over-long key is not hashed: nobody looks at the owner of a request that only earns its item error)
@@ -112,53 +109,10 @@ template <bool ROWS> __global__ __launch_bounds__(FR_TILE) void k_mx_count(MxIn 
         e = stay || owner >= A.world ? A.self : owner;
         A.own[i] = stay ? (uint8_t)(owner == A.self) : (uint8_t)1;   // (forwarded or owned here: evaluated as the owner, gubernator.go:247-256, :486)
     }
-    // the four-ballot trick of k_fr_count (lanes behind the generation's end carry 0xff and are in nobody's group)
-    unsigned long long same = __ballot(e <= 15u);
-#pragma unroll
-    for (uint32_t b = 0; b < 4; ++b) { const unsigned long long m = __ballot((e >> b) & 1u); same &= ((e >> b) & 1u) ? m : ~m; }
-    if (e > 15u) same = 0ull;
-    uint32_t rank = (uint32_t)__popcll(same & ((1ull << lane) - 1ull));
-    if (same && rank == 0) wtot[wave][e] = (uint32_t)__popcll(same);
-    __syncthreads();
-    if (i < A.n) {
-        for (uint32_t w = 0; w < wave; ++w) rank += wtot[w][e];
-        A.er[i] = (uint16_t)(e << FR_RANK_BITS | rank);
-    }
-    if (tid < MULTI_MEM_MAX) {
-        uint32_t c = 0;
-        for (uint32_t w = 0; w < FR_TILE / 64; ++w) c += wtot[w][tid];
-        A.tile_cnt[blockIdx.x * MULTI_MEM_MAX + tid] = c;
-    }
+    route_rank_tile(e, A.M, i, A.n);
 }
 
-// k_fr_scan's form — four workgroups, one per four destinations; thread t takes `per` consecutive tiles — without the front's key-width word
-__global__ __launch_bounds__(FR_SCAN_T) void k_mx_scan(MxIn A, uint32_t nt, uint32_t per) {
-    __shared__ uint32_t wsum[FR_SCAN_T / 64][4];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, q = blockIdx.x;
-    const uint32_t t0 = tid * per, t1 = t0 + per < nt ? t0 + per : nt;
-    uint32_t m0 = 0, m1 = 0, m2 = 0, m3 = 0;
-#pragma unroll 1
-    for (uint32_t t = t0; t < t1; ++t) { const uint4 v = ((const uint4*)(A.tile_cnt + (size_t)t * MULTI_MEM_MAX))[q]; m0 += v.x; m1 += v.y; m2 += v.z; m3 += v.w; }
-    const uint32_t i0 = (uint32_t)wave_incl_scan_i32((int)m0), i1 = (uint32_t)wave_incl_scan_i32((int)m1);
-    const uint32_t i2 = (uint32_t)wave_incl_scan_i32((int)m2), i3 = (uint32_t)wave_incl_scan_i32((int)m3);
-    if (lane == 63) { wsum[wave][0] = i0; wsum[wave][1] = i1; wsum[wave][2] = i2; wsum[wave][3] = i3; }
-    __syncthreads();
-    uint32_t e0 = i0 - m0, e1 = i1 - m1, e2 = i2 - m2, e3 = i3 - m3;
-    for (uint32_t w = 0; w < wave; ++w) { e0 += wsum[w][0]; e1 += wsum[w][1]; e2 += wsum[w][2]; e3 += wsum[w][3]; }
-#pragma unroll 1
-    for (uint32_t t = t0; t < t1; ++t) {
-        const uint4 v = ((const uint4*)(A.tile_cnt + (size_t)t * MULTI_MEM_MAX))[q];
-        ((uint4*)(A.tile_base + (size_t)t * MULTI_MEM_MAX))[q] = make_uint4(e0, e1, e2, e3);
-        e0 += v.x; e1 += v.y; e2 += v.z; e3 += v.w;
-    }
-    if (tid < 4) {
-        uint32_t all = 0;
-        for (uint32_t w = 0; w < FR_SCAN_T / 64; ++w) all += wsum[w][tid];
-        A.ctl->tot[4 * q + tid] = all;
-        // (relaxed, system scope: the word carries the call's sequence number, the host needs no fence from the device — FrontHost)
-        __hip_atomic_store(&A.host->w[4 * q + tid], (unsigned long long)A.seq << 32 | all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
+__global__ __launch_bounds__(FR_SCAN_T) void k_mx_scan(MxIn A, uint32_t nt, uint32_t per) { route_scan(A.M, A.seq, nt, per); }
 
 // LDS: the tile's requests in the destinations' order (2 KB) + FrTile.  Sorted element j gathers its request's columns (the tile's 1 024
 // requests: lines its neighbours load too) and writes record dofs[dest] + j: consecutive threads, consecutive records, whole sectors.
@@ -166,13 +120,13 @@ template <bool ROWS> __global__ __launch_bounds__(256) void k_mx_pack(MxIn A) {
     __shared__ FrTile T;
     __shared__ uint16_t src[FR_TILE];
     const uint32_t tile = blockIdx.x, tid = threadIdx.x, i0 = tile * FR_TILE + tid;
-    fr_tile_bases(T, A.ctl, A.tile_cnt, A.tile_base, tile);
+    fr_tile_bases(T, A.M, tile);
 #pragma unroll
     for (int k = 0; k < FR_PER; ++k) {
         const uint32_t i = i0 + k * 256u;
         if (i >= A.n) continue;
-        const uint32_t er = A.er[i], p = T.lbase[er >> FR_RANK_BITS] + (er & ((1u << FR_RANK_BITS) - 1u));
-        if (p < FR_TILE) src[p] = (uint16_t)(tid + k * 256u);
+        const uint32_t p = fr_place(T, A.M.er[i]);
+        if (p != 0xffffffffu) src[p] = (uint16_t)(tid + k * 256u);
     }
     __syncthreads();
     uint32_t dd[FR_PER];
@@ -237,7 +191,7 @@ __global__ __launch_bounds__(256) void k_mx_apack(MxAns S) {
 
 // LDS: the tile's answer records in slice order (32 KB) + FrTile: four workgroups of four waves per CU.
 struct MxOut {
-    uint32_t n; const uint16_t* er; const uint32_t *tile_cnt, *tile_base; const FrontCtl* ctl;
+    uint32_t n; RouteMap M;
     const uint8_t* ans;                                              // the answer records as they came back: the send buffer's order
     uint8_t *status, *err; int64_t *limit, *remaining, *reset_time; // the caller's result arrays, arrival order
 };
@@ -245,7 +199,7 @@ __global__ __launch_bounds__(256) void k_mx_out(MxOut A) {
     __shared__ FrTile T;
     __shared__ uint4 stg[FR_TILE][2];
     const uint32_t tile = blockIdx.x, tid = threadIdx.x, i0 = tile * FR_TILE + tid;
-    fr_tile_bases(T, A.ctl, A.tile_cnt, A.tile_base, tile);
+    fr_tile_bases(T, A.M, tile);
     uint32_t dd[FR_PER];
     fr_sorted_places(T, A.n, dd);
 #pragma unroll
@@ -259,8 +213,8 @@ __global__ __launch_bounds__(256) void k_mx_out(MxOut A) {
     for (int k = 0; k < FR_PER; ++k) {
         const uint32_t i = i0 + k * 256u;
         if (i >= A.n) continue;
-        const uint32_t er = A.er[i], p = T.lbase[er >> FR_RANK_BITS] + (er & ((1u << FR_RANK_BITS) - 1u));
-        if (p >= FR_TILE) continue;
+        const uint32_t p = fr_place(T, A.M.er[i]);
+        if (p == 0xffffffffu) continue;
         const uint4 x = stg[p][0], y = stg[p][1];
         A.status[i] = (uint8_t)x.x; A.err[i] = (uint8_t)(x.x >> 8);
         A.limit[i] = (int64_t)((uint64_t)x.z | (uint64_t)x.w << 32);

@@ -84,7 +84,7 @@ extern "C" int guber_mesh_create_local(guber_front_t* const* fronts, uint32_t n_
     std::vector<uint8_t> o8(npts);
     for (uint32_t j = 0; j < npts; ++j) o8[j] = (uint8_t)oo[j];
     m->ranks.resize(n_ranks);
-    const size_t tiles = ((size_t)max_n + FR_TILE - 1) / FR_TILE, cap_in = (size_t)n_ranks * max_n, rb = m->rec_bytes;
+    const size_t cap_in = (size_t)n_ranks * max_n, rb = m->rec_bytes;
     for (uint32_t r = 0; r < n_ranks; ++r) {
         auto& R = m->ranks[r];
         guber_front* f = fronts[r];
@@ -93,35 +93,38 @@ extern "C" int guber_mesh_create_local(guber_front_t* const* fronts, uint32_t n_
         if ((uint64_t)std::min<size_t>(f->cap, cap_in) * rb > 0xffffffffull) return fail(GUBER_E_BATCH_TOO_LARGE, "guber_mesh: a front's generation of key rows exceeds 4 GB");
         if (n_ranks == 1) continue;                                  // (one rank: the front alone, no exchange)
         if (hipSetDevice(R.device) != hipSuccess) return fail(GUBER_E_HIP, "hipSetDevice");
-        const size_t scratch = front_col((size_t)max_n * 2) + front_col(max_n) + 2 * front_col(tiles * MULTI_MEM_MAX * 4) + front_col(sizeof(FrontCtl));
-        const size_t cols = 5 * front_col(cap_in * 8) + 2 * front_col(cap_in * 4) + 2 * front_col(cap_in) +      // the inflow's request columns
-                            3 * front_col(cap_in * 8) + 2 * front_col(cap_in);                                 // its answers
-        if (R.scratch.ensure(scratch) || R.send.ensure((size_t)max_n * rb + 64) || R.recv.ensure(cap_in * rb + 64) || R.cols.ensure(cols) ||
-            R.ans_send.ensure(cap_in * MX_ANS + 64) || R.ans_recv.ensure((size_t)max_n * MX_ANS + 64) || R.ring_h.ensure(npts) || R.ring_o.ensure(npts) ||
-            R.host.ensure(1)) return GUBER_E_NOMEM;
+        // the inflow's request columns and its answers
+        auto carve_cols = [&](uint8_t* base) {
+            ColCarver c{(uintptr_t)base};
+            MxUnpack& U = R.un;
+            U.hits = c.take<int64_t>(cap_in); U.limit = c.take<int64_t>(cap_in); U.duration = c.take<int64_t>(cap_in);
+            U.burst = c.take<int64_t>(cap_in); U.created_at = c.take<int64_t>(cap_in);
+            U.key_len = c.take<uint32_t>(cap_in); U.behavior = c.take<uint32_t>(cap_in);
+            U.algorithm = c.take<uint8_t>(cap_in); U.is_owner = c.take<uint8_t>(cap_in);
+            MxAns& S = R.an;
+            S.limit = c.take<int64_t>(cap_in); S.remaining = c.take<int64_t>(cap_in); S.reset_time = c.take<int64_t>(cap_in);
+            S.status = c.take<uint8_t>(cap_in); S.err = c.take<uint8_t>(cap_in);
+            return (size_t)(c.at - (uintptr_t)base);
+        };
+        // the routing scratch, and own[] behind it (the routing scratch is carved as one piece)
+        auto carve_scratch = [&](uint8_t* base) {
+            ColCarver c{(uintptr_t)base};
+            R.in.M = route_carve(c, max_n, R.host.p); R.in.own = c.take<uint8_t>(max_n);
+            return (size_t)(c.at - (uintptr_t)base);
+        };
+        if (R.scratch.ensure(carve_scratch(nullptr)) || R.send.ensure((size_t)max_n * rb + 64) || R.recv.ensure(cap_in * rb + 64) ||
+            R.cols.ensure(carve_cols(nullptr)) || R.ans_send.ensure(cap_in * MX_ANS + 64) || R.ans_recv.ensure((size_t)max_n * MX_ANS + 64) ||
+            R.ring_h.ensure(npts) || R.ring_o.ensure(npts) || R.host.ensure(1)) return GUBER_E_NOMEM;
         memset((void*)R.host.p, 0, sizeof(FrontHost));
+        carve_cols(R.cols.p); carve_scratch(R.scratch.p);
         MxIn& A = R.in;
-        uint8_t* p = R.scratch.p;
-        A.er = (uint16_t*)p; p += front_col((size_t)max_n * 2); A.own = p; p += front_col(max_n);
-        A.tile_cnt = (uint32_t*)p; p += front_col(tiles * MULTI_MEM_MAX * 4); A.tile_base = (uint32_t*)p; p += front_col(tiles * MULTI_MEM_MAX * 4);
-        A.ctl = (FrontCtl*)p;
-        A.host = R.host.p; A.send = R.send.p; A.rec_bytes = m->rec_bytes;
+        A.send = R.send.p; A.rec_bytes = m->rec_bytes;
         A.self = r; A.world = n_ranks; A.max_key = R.max_key; A.npts = npts; A.kind = m->kind; A.ring_lds = m->ring_lds ? 1u : 0u;
         A.ring_hash = R.ring_h.p; A.ring_owner = R.ring_o.p;
-        p = R.cols.p;
-        MxUnpack& U = R.un;
-        U.rec_bytes = m->rec_bytes; U.recv = R.recv.p;
-        U.hits = (int64_t*)p; p += front_col(cap_in * 8); U.limit = (int64_t*)p; p += front_col(cap_in * 8); U.duration = (int64_t*)p; p += front_col(cap_in * 8);
-        U.burst = (int64_t*)p; p += front_col(cap_in * 8); U.created_at = (int64_t*)p; p += front_col(cap_in * 8);
-        U.key_len = (uint32_t*)p; p += front_col(cap_in * 4); U.behavior = (uint32_t*)p; p += front_col(cap_in * 4);
-        U.algorithm = p; p += front_col(cap_in); U.is_owner = p; p += front_col(cap_in);
-        MxAns& S = R.an;
-        int64_t* a_limit = (int64_t*)p; p += front_col(cap_in * 8); int64_t* a_rem = (int64_t*)p; p += front_col(cap_in * 8); int64_t* a_reset = (int64_t*)p; p += front_col(cap_in * 8);
-        uint8_t* a_status = p; p += front_col(cap_in); uint8_t* a_err = p; p += front_col(cap_in);
-        S.status = a_status; S.err = a_err; S.limit = a_limit; S.remaining = a_rem; S.reset_time = a_reset; S.out = R.ans_send.p;
+        R.un.rec_bytes = m->rec_bytes; R.un.recv = R.recv.p; R.an.out = R.ans_send.p;
         HIPCHK(hipMemcpyAsync(R.ring_h.p, hh.data(), (size_t)npts * 8, hipMemcpyHostToDevice, R.st));
         HIPCHK(hipMemcpyAsync(R.ring_o.p, o8.data(), npts, hipMemcpyHostToDevice, R.st));
-        HIPCHK(hipMemsetAsync(A.ctl, 0, sizeof(FrontCtl), R.st));
+        HIPCHK(hipMemsetAsync(A.M.ctl, 0, sizeof(FrontCtl), R.st));
         HIPCHK(hipMemsetAsync(R.recv.p, 0, cap_in * rb + 64, R.st));      // (key rows are read as 8-byte words: every byte of a row is defined)
         HIPCHK(hipEventCreateWithFlags(&R.ev_pack, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&R.ev_ans, hipEventDisableTiming));
@@ -140,21 +143,8 @@ static int mesh_exchange_counts(guber_mesh* m, std::vector<uint32_t>& table) {
     for (uint32_t s = 0; s < W; ++s) {
         auto& R = m->ranks[s];
         if (R.n == 0) continue;
-        auto reported = [&]() {
-            for (uint32_t q = 0; q < (uint32_t)MULTI_MEM_MAX; ++q)
-                if ((uint32_t)(__atomic_load_n((volatile unsigned long long*)&R.host.p->w[q], __ATOMIC_ACQUIRE) >> 32) != m->seq) return false;
-            return true;
-        };
-        uint32_t spins = 0;
-        while (!reported()) {
-            if (++spins > 2000) {
-                std::this_thread::yield();
-                if ((spins & 0x3ffu) == 0) {
-                    if (hipSetDevice(R.device) != hipSuccess) return fail(GUBER_E_HIP, "hipSetDevice");
-                    if (hipStreamQuery(R.st) != hipErrorNotReady && !reported()) return fail(GUBER_E_HIP, "guber_mesh: the routing of a generation did not report");
-                }
-            }
-        }
+        const int rc = route_wait_reported(R.host.p, MULTI_MEM_MAX, m->seq, R.device, R.st, "guber_mesh: the routing of a generation did not report");
+        if (rc) return rc;
         uint64_t tot = 0;
         for (uint32_t o = 0; o < (uint32_t)MULTI_MEM_MAX; ++o) {
             const uint32_t c = (uint32_t)R.host.p->w[o];
@@ -296,7 +286,7 @@ static int mesh_eval(guber_mesh* m, const guber_batch_t* gens, const guber_mesh_
         if (R.n) {
             { const int r2 = mesh_exchange(m, table, s, true); if (r2) return r2; }
             MxOut O{};
-            O.n = R.n; O.er = R.in.er; O.tile_cnt = R.in.tile_cnt; O.tile_base = R.in.tile_base; O.ctl = R.in.ctl; O.ans = R.ans_recv.p;
+            O.n = R.n; O.M = R.in.M; O.ans = R.ans_recv.p;
             O.status = results[s].status; O.err = results[s].err; O.limit = results[s].limit; O.remaining = results[s].remaining; O.reset_time = results[s].reset_time;
             hipLaunchKernelGGL(k_mx_out, dim3((R.n + FR_TILE - 1u) / FR_TILE), dim3(256), 0, R.st, O);
             if (hipGetLastError() != hipSuccess) return fail(GUBER_E_HIP, "kernel launch");

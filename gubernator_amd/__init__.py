@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("GUBER_HIP_LIB") or os.path.join(_HERE, "libguber_hip.
 # every symbol include/guber_gpu.h declares
 ABI_SYMBOLS = [
     "guber_engine_create", "guber_engine_destroy", "guber_eval_batch", "guber_eval_batch_dev", "guber_add_items",
-    "guber_get_item", "guber_remove_item", "guber_size", "guber_dump", "guber_stats", "guber_synchronize",
+    "guber_get_item", "guber_remove_item", "guber_size", "guber_dump", "guber_stats", "guber_recency_info", "guber_synchronize",
     "guber_alloc_pinned", "guber_free_pinned", "guber_ring_create", "guber_ring_destroy", "guber_ring_route",
     "guber_ring_route_dev", "guber_ring_points", "guber_gregorian_expiration", "guber_gregorian_duration",
     "guber_xxhash64", "guber_fnv1_64", "guber_fnv1a_64", "guber_strerror", "guber_item_strerror",
@@ -43,6 +43,7 @@ FLAG_TEST_WEAK_HASH, FLAG_TEST_FORCE_RADIX, FLAG_TEST_CAREFUL, FLAG_GLOBAL, FLAG
 FLAG_TEST_FORCE_PART, FLAG_NO_PART = 64, 128
 FLAG_TEST_LATE_COUNTERS = 256    # csrc/guber_test_flags.h: recency stamps, epochs and the snapshot ring's sequence start just below their wraps
 FLAG_TEST_FIXED_ARENA = 512      # csrc/guber_test_flags.h: the long-key arena neither grows nor asks for a rebuild
+FLAG_TEST_LAST_STAMPS = 1024     # csrc/guber_test_flags.h: the next recency stamp starts 4 096 below the end of the 53 bits (2^53 - 4096)
 
 _lib = None
 
@@ -81,6 +82,8 @@ def lib():
         L.guber_dump.argtypes = [C.c_void_p, C.POINTER(GuberItem), C.c_uint64, C.c_void_p, C.c_uint64,
                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.guber_stats.argtypes = [C.c_void_p, C.POINTER(GuberStats)]
+        if hasattr(L, "guber_recency_info"):             # (a stand-in library of the tests may not have it)
+            L.guber_recency_info.argtypes = [C.c_void_p, C.POINTER(abi.GuberRecencyInfo)]
         L.guber_synchronize.argtypes = [C.c_void_p]
         L.guber_compact.argtypes = [C.c_void_p, C.c_int64]
         L.guber_set_clock.argtypes = [C.c_void_p, C.c_int64]
@@ -390,6 +393,13 @@ class Engine:
         s = GuberStats()
         _check(lib().guber_stats(self.h, C.byref(s)))
         return {f[0]: getattr(s, f[0]) for f in GuberStats._fields_}
+
+    def recency_info(self):
+        """guber_recency_info: next_stamp (the next recency stamp the engine hands out), renumbers (times the live items' stamps were
+        renumbered 1..live at the end of the 53 bits), last_live (items the last renumbering numbered)"""
+        s = abi.GuberRecencyInfo()
+        _check(lib().guber_recency_info(self.h, C.byref(s)))
+        return {"next_stamp": s.next_stamp, "renumbers": s.renumbers, "last_live": s.last_live}
 
     def global_take(self, role_mask=6):
         """Pending GLOBAL rows of the requested roles (bit 1 = hits for the owner, bit 2 = owner updates) as

@@ -50,6 +50,11 @@ class GuberStats(C.Structure):
                 ("eviction_passes", C.c_uint64), ("tail_rebuilds", C.c_uint64), ("batch_cuts", C.c_uint64)]
 
 
+class GuberRecencyInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("next_stamp", C.c_uint64), ("renumbers", C.c_uint64),
+                ("last_live", C.c_uint64)]
+
+
 class GuberGlobalRows(C.Structure):
     _fields_ = [("n", C.c_uint32), ("key_stride", C.c_uint32), ("key_bytes", C.c_void_p), ("key_len", C.c_void_p),
                 ("hits", C.c_void_p), ("limit", C.c_void_p), ("duration", C.c_void_p), ("burst", C.c_void_p),

@@ -38,7 +38,9 @@ static LruKeys lru_keys_of(const BatchView& B) {
 }
 // The tail list: every live item's (stamp, slot), sorted by stamp — one table scan and one radix sort, then good for as many
 // batches as it has valid entries left (an entry is valid while its bucket still carries that stamp).
-static int lru_rebuild(guber_engine* e) {
+// renumber (stamps_ensure, the end of the 53 bits): the sorted list holds EVERY live item, so in the same pass entry i and its bucket get the
+// stamp 1 + i (k_lru_renumber) and the engine goes on from live + 1 — the order is what it was, the list is valid and complete.
+static int lru_rebuild(guber_engine* e, bool renumber = false) {
     int rc = engine_refresh_counters(e);
     if (rc) return rc;
     const uint64_t live = (uint64_t)std::max<long long>(e->last_ctr.size, 0);
@@ -58,11 +60,32 @@ static int lru_rebuild(guber_engine* e) {
         if (e->lru_sort_tmp.ensure(tmp + 16)) return GUBER_E_NOMEM;
         HIPCHK(hipcub::DeviceRadixSort::SortPairs(e->lru_sort_tmp.p, tmp, e->lru_tstamp_in.p, e->lru_tstamp.p, e->lru_tslot_in.p, e->lru_tslot.p, (int)cnt, 0, 53, st));
     }
+    if (renumber && cnt) {                                           // (every allocation is behind us: from here on nothing fails for memory)
+        hipLaunchKernelGGL(k_lru_renumber, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, e->T, e->lru_tstamp.p, e->lru_tslot.p, cnt);
+        HIPCHK(hipGetLastError());
+    }
     LruCtl c{}; c.cursor = 0; c.tail_n = cnt;
     HIPCHK(hipMemcpyAsync(e->lru_ctl.p, &c, sizeof(c), hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
     e->lru_tail_ok = true; e->lru_rebuilds++;
+    if (renumber) { e->seq_next = cnt + 1; e->renumbers++; e->renumber_live = cnt; }
     return 0;
+}
+// The one check of every path that takes stamps: the n stamps the call is about to take (take_stamps: at least 1) must end at or below
+// REC_STAMP_MASK — rec_set_stamp would write stamp 2^53 as 0 and the newest item would look like the oldest.  Exact and per call: one 64-bit
+// compare on the host, nothing on the device.  When they do not fit, the live items are renumbered first (lru_rebuild above: it drains the
+// engine's stream, so it is ordered behind every batch already enqueued, reads the exact counters — a snapshot that was to ride on a batch is
+// forgotten with every other one, fold_counters — and counts as a tail rebuild).  It is HARD maintenance: with defer_hard (maintain()) the
+// caller is holding a k_eval3 back — *defer_hard = true, nothing is done, the caller launches it and comes again.  An allocation that fails
+// leaves the table as it was and fails the call: no stamp past the mask is ever handed out.
+static bool stamps_fit(const guber_engine* e, uint64_t n) { return e->seq_next + (n ? n : 1) <= REC_STAMP_MASK + 1; }
+static int stamps_ensure(guber_engine* e, uint64_t n, bool* defer_hard = nullptr) {
+    if (stamps_fit(e, n)) return 0;
+    if (defer_hard) { *defer_hard = true; return 0; }
+    e->lru_tail_ok = false;                                          // (a rebuild that fails half-way leaves no list to trust)
+    const int rc = lru_rebuild(e, true);
+    if (rc) return rc;
+    return stamps_fit(e, n) ? 0 : fail(GUBER_E_INVALID_ARG, "more recency stamps in one call than there are");
 }
 // The pre-pass of a call that may overflow the cache: n requests (or n = 0: only bring the cache down to cache_size).  On return
 // *status is LRU_NONE / LRU_APPLIED (the buckets that leave are absent, the counters adjusted: evaluate the batch) or LRU_CUT
@@ -337,6 +360,12 @@ static int launch_batch(guber_engine* e, const BatchView& B, const ResultView& R
     // (a batch the kernels read in place from host memory: its offsets say exactly what its long keys can add to the arena)
     const bool plain_off = host_resident && !B.key_width && !B.key_stride && !B.key_len && B.key_off;
     ArenaHint hint(e, plain_off && e->arena_hint == ~0ull ? host_arena_bytes(e, B.key_off, B.n) : ~0ull);
+    // The stamps of the WHOLE batch, looked at before its pre-pass: a renumbering that is due comes first, and the pre-pass then works on the
+    // complete list it leaves (one rebuild for both).  The preludes below look again, for their own piece (maintain()): a renumbering there —
+    // between a pre-pass and its batch, or between two pieces of a cut or split batch — is just as correct, because a pre-pass has completed
+    // when it returns and has only made buckets absent, the order of the live items is kept, the tail list is rewritten in the same pass, and
+    // the piece's stamps are handed out after it: newer than everything, as before.
+    { const int rc = stamps_ensure(e, B.n); if (rc) return rc; }
     if (!lru_may_bind(e, B.n)) return launch_batch_inner(e, B, R, host_resident);
     if (B.n > e->max_batch) return fail(GUBER_E_BATCH_TOO_LARGE, "batch larger than guber_config_t.max_batch");
     uint8_t* const sf0 = e->W.store_flags; Rec* const sa0 = e->W.store_after;

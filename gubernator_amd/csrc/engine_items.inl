@@ -144,6 +144,8 @@ static int item_lookup(guber_engine* e, const uint8_t* key, uint32_t key_len, in
     int rc = d_key.ensure(key_len + 16) | d_rec.ensure(1) | d_found.ensure(1);
     auto cleanup = [&]() {};
     if (rc) return GUBER_E_NOMEM;
+    rc = stamps_ensure(e, 1);                                 // (GetItem and Remove take one stamp without passing through maintain())
+    if (rc) return rc;
     std::vector<uint8_t> kb(key_len + 16, 0);
     memcpy(kb.data(), key, key_len);
     Rec hrec; int hfound = 0;
@@ -239,6 +241,15 @@ extern "C" int guber_stats(guber_engine_t* e, guber_stats_t* out) {
     out->tags_used = c.tags_used; out->batches = e->batches; out->retries = c.retries; out->compactions = e->compactions;
     out->small_batches = e->small_batches; out->fused_batches = e->fused_batches;
     out->eviction_passes = e->lru_applied; out->tail_rebuilds = e->lru_rebuilds; out->batch_cuts = e->lru_cuts;
+    return GUBER_OK;
+}
+// host state only (set_device launches an evaluation that is being held back first, like every entry point)
+extern "C" int guber_recency_info(guber_engine_t* e, guber_recency_info_t* out) {
+    if (!e || !out) return fail(GUBER_E_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
+    out->struct_size = (uint32_t)sizeof(*out); out->reserved = 0;
+    out->next_stamp = e->seq_next; out->renumbers = e->renumbers; out->last_live = e->renumber_live;
     return GUBER_OK;
 }
 extern "C" int64_t guber_size(guber_engine_t* e) {

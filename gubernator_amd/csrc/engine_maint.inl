@@ -97,6 +97,15 @@ static int evict_to_size(guber_engine* e, int64_t now_ms) {
 static int maintain(guber_engine* e, uint64_t incoming, int64_t now_ms, bool batch_follows, bool* defer_hard, uint64_t arena_bytes) {
     const uint64_t tag_limit = e->slots - e->slots / 8;   // keep >= 1/8 of the entries free
     const uint64_t hard_size = e->cache_size + std::max<uint64_t>(e->cache_size / 2, 4ull * e->max_batch);
+    // The stamps the call is about to take (a call with incoming == 0 takes none): every caller's take_stamps(e, incoming) follows this, so
+    // the check lives here, before the early return.  A prelude comes through here for the eviction pre-pass's batch and for every piece of a
+    // cut or split batch (launch_batch), so a renumbering may fall between a pre-pass and its batch or between two pieces: the pre-pass has
+    // completed by then (it ends with a synchronisation) and only made buckets absent; the renumbering keeps the order of the live ones
+    // and rewrites the tail list in the same pass, so the batch's stamps — handed out after it — are newer than everything, as before.
+    if (incoming) {
+        const int rc = stamps_ensure(e, incoming, defer_hard);
+        if (rc || (defer_hard && *defer_hard)) return rc;
+    }
     if (e->rb_ride >= 0 && !batch_follows) {              // a snapshot that was to ride on a batch that never came: launch it now
         if (defer_hard) { *defer_hard = true; return 0; }
         const uint32_t i = (uint32_t)e->rb_ride;

@@ -164,6 +164,9 @@ struct guber_engine {
     // The recency order of LRUCache's list (lrucache.go:88-128) as request sequence numbers: a batch of n requests takes n stamps
     // (request i the i-th), Add one per item, GetItem one; every bucket carries the stamp of its last touch (rec_stamp, 53 bits).
     uint64_t seq_next = 1;     // the next stamp to hand out
+    // The stamp space does not end: the call that would take a stamp above REC_STAMP_MASK first renumbers the live items' stamps 1..live in
+    // their order (stamps_ensure, k_lru_renumber) and goes on from live + 1.  guber_recency_info reports these.
+    uint64_t renumbers = 0, renumber_live = 0;
     // The exact victim order when the cache binds (guber_kernels_lru.h): the tail list (live items sorted by stamp), the pre-pass's
     // control block and scratch.  Allocated by the first call that may overflow the cache.
     DevBuf<LruCtl> lru_ctl; PinBuf<LruCtl> lru_hctl;
@@ -392,6 +395,7 @@ extern "C" int guber_engine_create(const guber_config_t* cfg, guber_engine_t** o
     if (cfg->flags & GUBER_FLAG_TEST_LATE_COUNTERS) {   // (guber_test_flags.h: the counters where production is after seconds to days)
         e->seq_next = GUBER_TEST_LATE_SEQ_NEXT; e->epoch = GUBER_TEST_LATE_EPOCH; e->fast_epoch16 = GUBER_TEST_LATE_EPOCH16; e->rb_seq = GUBER_TEST_LATE_RB_SEQ;
     }
+    if (cfg->flags & GUBER_FLAG_TEST_LAST_STAMPS) e->seq_next = GUBER_TEST_LAST_SEQ_NEXT;   // (after the epochs' flag: this stamp start wins)
     e->use_part = !(cfg->flags & GUBER_FLAG_NO_PART) && !e->force_radix && !e->always_careful;
     // GUBER_PIPELINE: "claims" = never the owner-partitioned pipeline, "part" = also for a batch launched on its own; default: the
     // owner-partitioned pipeline when several tables share the launches (where it is faster: profiles/r04_*), claims otherwise

@@ -319,4 +319,19 @@ __global__ __launch_bounds__(256) void k_lru_gather(Table T, uint64_t slots, uns
     if (k < cap) { stamp[k] = rec_stamp(r); slot[k] = (uint32_t)s; }
 }
 
+// ---- the end of the 53 bits: the tail list just sorted (EVERY live item, oldest first) gets dense stamps again — entry i and its bucket the
+// stamp 1 + i, so the order of the list is what it was and the engine goes on handing out stamps from n + 1.  One thread per entry: the sorted
+// columns are read coalesced, the bucket's record is one scattered 64-byte sector of which the word of meta and pad is rewritten (kind, status
+// and algorithm stay: REC_META_MASK).  Nothing else runs on the table (the host has drained the stream, engine_batch.inl lru_rebuild), every
+// slot is in the list once: plain stores, no atomics.  The list's stamp column is rewritten in the same launch, so the list stays valid.
+__global__ __launch_bounds__(256) void k_lru_renumber(Table T, unsigned long long* t_stamp, const uint32_t* t_slot, unsigned long long n) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    Rec* r = &T.buckets[t_slot[i]].rec;
+    const unsigned long long st = 1ull + i;
+    r->meta = (r->meta & REC_META_MASK) | ((uint32_t)(st >> 32) << 11);
+    r->pad = (uint32_t)st;
+    t_stamp[i] = st;
+}
+
 }  // namespace guber

@@ -10,6 +10,11 @@
 #define GUBER_FLAG_TEST_FORCE_PART 64u  /* every batch (also <= 256 requests, also host-resident ones) takes the owner-partitioned three-launch pipeline */
 #define GUBER_FLAG_TEST_LATE_COUNTERS 256u /* the engine's counters start where production is after seconds to days (the values below): nothing else changes */
 #define GUBER_FLAG_TEST_FIXED_ARENA 512u /* the long-key arena keeps its first size: no bound asks for a rebuild, no rebuild grows it — so that a full arena and its per-item refusal can be reached */
+#define GUBER_FLAG_TEST_LAST_STAMPS 1024u /* the engine's next recency stamp starts 4 096 below the END of the 53 bits (the value below): nothing else changes.  With
+                                             GUBER_FLAG_TEST_LATE_COUNTERS (the epochs) this flag's stamp start wins */
+// Where an engine created with GUBER_FLAG_TEST_LAST_STAMPS starts: the call that would hand out a stamp above REC_STAMP_MASK renumbers the live
+// items' stamps 1..live first (engine_batch.inl stamps_ensure; tests/stamp_end_cases.py positions that call by arithmetic of its own).
+#define GUBER_TEST_LAST_SEQ_NEXT ((1ull << 53) - 4096ull) /* guber_engine::seq_next */
 // Where an engine created with GUBER_FLAG_TEST_LATE_COUNTERS starts (guber_engine_create; tests/late_counters.py mirrors the four values and
 // tests/test_late_counters_cpu.py holds the mirror to this file).  The next 4 096 recency stamps have Rec::pad near 0xffffffff and the twenty
 // lower high bits set; stamp 2^52 clears pad, flips every one of those bits and sets bit 52 (Rec::meta bit 31).  A batch takes one epoch and,

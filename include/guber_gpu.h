@@ -81,7 +81,7 @@ typedef struct guber_engine guber_engine_t;
 #define GUBER_FLAG_GLOBAL 8u          /* keep per-bucket pending GLOBAL hits / updates (guber_global_take) */
 #define GUBER_FLAG_NO_PART 128u        /* never take the owner-partitioned pipeline: batches of 257 .. 65 536 requests run the
                                           two-launch pipeline with per-batch claims (round 3's; kept as the retry round) */
-/* (bits 1, 2, 4, 32, 64, 256 and 512 select code paths for the test suite — gubernator_amd/csrc/guber_test_flags.h —, bit 16 is accepted and
+/* (bits 1, 2, 4, 32, 64, 256, 512 and 1024 select code paths for the test suite — gubernator_amd/csrc/guber_test_flags.h —, bit 16 is accepted and
  *  ignored: a binding passes none of them) */
 
 /* Engine configuration.  Replaces Config.{CacheSize,Workers,CacheFactory}
@@ -448,6 +448,11 @@ int guber_front_store_stats(guber_front_t* f, guber_front_store_stats_t* out);
  *      rest as batches of their own (guber_stats_t.batch_cuts counts them): exact by construction
  *      (test_requests_that_change_the_lists_length_are_evaluated_on_their_own; round 5 had documented the second kind as not
  *      reproduced).  Nothing of lrucache.go:88-171 is left unreproduced.
+ *      The sequence numbers do not run out, however long the engine lives: the call that would take a number above 2^53 - 1 (one
+ *      table at 2.5 G decisions/s: after about 42 days) first gives the live items the numbers 1 .. live in their order — the
+ *      table scan and sort of a tail rebuild (it counts as one) and one more launch — and goes on from live + 1; who is evicted
+ *      is what it would have been (guber_recency_info; tests/stamp_end_cases.py).  Numbers of different engines were never
+ *      comparable and are not now.
  *      Cost: nothing while live items + requests <= cache_size (size the cache with a batch of headroom); beyond that one
  *      pre-pass per batch (a dozen small launches and one stream synchronisation; the recency order of the live items comes
  *      from one table scan + sort per ~live/(2 x batch) batches: guber_stats_t.tail_rebuilds).
@@ -468,6 +473,15 @@ int guber_compact(guber_engine_t* e, int64_t now_ms);
 int guber_set_clock(guber_engine_t* e, int64_t now_ms);
 
 int guber_stats(guber_engine_t* e, guber_stats_t* out);
+/* The recency stamps ("bounded cache" above): where the engine is in its 53 bits and how often it has started them again.  Host state
+ * only: no launch, no synchronisation. */
+typedef struct guber_recency_info {
+    uint32_t struct_size; uint32_t reserved;
+    uint64_t next_stamp;      /* the next recency stamp this engine hands out */
+    uint64_t renumbers;       /* times the live items' stamps were renumbered 1..live */
+    uint64_t last_live;       /* live items the last renumbering numbered */
+} guber_recency_info_t;
+int guber_recency_info(guber_engine_t* e, guber_recency_info_t* out);
 int guber_synchronize(guber_engine_t* e);
 
 /* ---- per-kernel timing for the roofline report (replaces the reference's prometheus

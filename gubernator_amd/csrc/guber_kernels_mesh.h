@@ -11,7 +11,7 @@ namespace guber {
 //   k_mx_count   per request: fnv1 / fnv1a of the key, the ring's point -> destination rank, its rank among the tile's requests of that
 //                destination (stable: arrival order); per tile of 1 024 requests the requests per destination.  GLOBAL requests
 //                (gubernator.go:258-270: never forwarded) and keys the ring cannot place (empty, over-long) have destination self;
-//                own[i] = the is_owner the request is evaluated with
+//                own[i] = the is_owner the request is evaluated with; item_owner[i] (optional) = the peer the ring names, 0xFF = none
 //   k_mx_scan    route_scan: tile bases and the totals per destination, to ctl->tot and — stamped with the call's sequence
 //                number — to pinned memory
 //   k_mx_pack    the tile sorted by destination in LDS (the place is computed: lbase[dest] + rank), one fixed-width record per request
@@ -54,6 +54,7 @@ struct MxIn {
     RouteMap M; uint8_t* own;
     uint8_t* send; uint32_t rec_bytes;
     uint32_t key_stride; const uint32_t* key_len;                   // <true> only: the rows' distance (a multiple of 8) and the keys' lengths
+    uint8_t* item_owner;                                             // optional (null: not wanted): [n] the RING's owner of request i — not its destination — 0xFF where the ring cannot place the key
 };
 
 // fnv1 / fnv1a (segmentio/fasthash, as replicated_hash.go uses them) over a key of len < 32 bytes held in four words
@@ -108,8 +109,20 @@ template <bool ROWS> __global__ __launch_bounds__(FR_TILE) void k_mx_count(MxIn 
         }
         e = stay || owner >= A.world ? A.self : owner;
         A.own[i] = stay ? (uint8_t)(owner == A.self) : (uint8_t)1;   // (forwarded or owned here: evaluated as the owner, gubernator.go:247-256, :486)
+        // who the ring names, for the caller that tells its client (metadata "owner", gubernator.go:267-268, :379-381): a GLOBAL request's too,
+        // although it stays; a key the ring cannot place (empty, over-long) has none.  As d_fwd in the front: stored only when wanted.
+        if (A.item_owner) A.item_owner[i] = (len == 0 || len > A.max_key) ? (uint8_t)0xffu : (uint8_t)owner;
     }
     route_rank_tile(e, A.M, i, A.n);
+}
+
+// one rank: no routing runs, and the ring has one peer — item_owner[i] = 0, or 0xFF for a key no ring places.  Rows only (lengths as
+// k_mx_count<true> reads them): the one caller that asks for the column hands over a decoder's rows.
+__global__ __launch_bounds__(256) void k_mx_owner_one(uint32_t n, const uint32_t* key_len, uint32_t key_stride, uint32_t max_key, uint8_t* item_owner) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t len = key_len[i];                                // (more than a row holds: over-long, as any length above max_key)
+    item_owner[i] = (len == 0 || len > max_key || len > key_stride) ? (uint8_t)0xffu : (uint8_t)0;
 }
 
 __global__ __launch_bounds__(FR_SCAN_T) void k_mx_scan(MxIn A, uint32_t nt, uint32_t per) { route_scan(A.M, A.seq, nt, per); }

@@ -680,4 +680,107 @@ __global__ __launch_bounds__(WE_T) void k_wire_enc(WireEnc E) {
     }
 }
 
+// ---- the same behind a MESH (guber_wire_dev_eval_mesh_enc): every answer that was not evaluated as the arrival rank's own carries
+// metadata{"owner": <the owner's address>} (gubernator.go:267-268, :379-381) — field 6, behind the four varint fields.  The answers lie
+// in arrival order (k_mx_out wrote them: no fwd), item_owner[] is k_mx_count's optional column: the peer the ring names, 0xFF = none.
+// The suffix is a constant per peer (wire::put_owner_suffix, built by the host once per call): the table is staged in LDS and an item's
+// metadata is a copy from there.  A forwarded item and a GLOBAL item answered from a non-owner's replica differ in their error texts
+// only, and an RPC with an item error is the host's as before (WIRE_ENC_RAW): this kernel does not look at behavior[].
+// PIECES.  An item is 2 .. RESP_OWNER_ITEM_MAX (315) bytes now, its length prefix one byte or two, so k_wire_enc's stage of 1 024 items
+// of 37 bytes cannot be kept.  A piece is WEO_P = 192 items, one per thread of three waves: the largest whole number of waves whose
+// worst case fits — 192 x 315 + 32 bytes of stage + 16 x 288 of suffixes + 80 = 65 200 of the 65 536 bytes a workgroup may hold
+// statically (256 items would need 80 KB).  Scheme as k_wire_enc: wave scan of the sizes, carry across pieces, whole 16-byte words out.
+constexpr uint32_t WEO_T = 192, WEO_P = WEO_T;
+constexpr uint32_t WEO_RANKS = 16;                                  // = MULTI_MEM_MAX: the ranks of a mesh
+constexpr uint32_t WEO_SFX_STRIDE = (wire::OWNER_SUFFIX_MAX + 15u) & ~15u;
+// where RPC r's bytes start when no item of the call takes more than item_max bytes (the host knows the call's longest suffix): as wire_enc_off
+GW_HD size_t wire_enco_off(uint32_t first, uint32_t r, uint32_t item_max) { return ((size_t)first * item_max + (size_t)r * 32u) & ~(size_t)15; }
+GW_HD size_t wire_enco_bytes(uint32_t items, uint32_t rpcs, uint32_t item_max) { return (size_t)items * item_max + (size_t)rpcs * 32u + 64u; }
+struct WireEncOwner {
+    WireEnc E;                                                       // (fwd is not read)
+    const uint8_t* item_owner; uint32_t self, n_ranks, item_max;
+    const uint8_t* sfx; const uint32_t* sfx_len;                     // HBM: [n_ranks][WEO_SFX_STRIDE] bytes, [n_ranks]
+};
+__global__ __launch_bounds__(WEO_T) void k_wire_enc_owner(WireEncOwner A) {
+    __shared__ alignas(16) uint8_t stage[WEO_P * wire::RESP_OWNER_ITEM_MAX + 32];
+    __shared__ alignas(16) uint8_t sfx[WEO_RANKS * WEO_SFX_STRIDE];
+    __shared__ uint32_t sfx_len[WEO_RANKS];
+    __shared__ uint32_t wsum[WEO_T / 64];
+    __shared__ uint32_t s_bad;
+    static_assert(sizeof(stage) + sizeof(sfx) + sizeof(sfx_len) + sizeof(wsum) + 4 <= 64 * 1024, "static LDS of a workgroup");
+    const WireEnc& E = A.E;
+    const uint32_t r = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t first = E.first[r];
+    const uint32_t count = E.status[r] == WIRE_OK ? E.count[r] : 0u;
+    if (count == 0u) { if (tid == 0) E.enc_len[r] = 0u; return; }
+    if (tid == 0) s_bad = 0u;
+    const uint32_t nr = A.n_ranks < WEO_RANKS ? A.n_ranks : WEO_RANKS;
+    for (uint32_t q = tid * 16u; q < nr * WEO_SFX_STRIDE; q += WEO_T * 16u) *(uint4*)(sfx + q) = *(const uint4*)(A.sfx + q);
+    if (tid < nr) sfx_len[tid] = A.sfx_len[tid];
+    __syncthreads();
+    const bool one_piece = count <= WEO_P;                             // (finds an item error from the loads it encodes from; a longer RPC looks first)
+    if (!one_piece) {
+        uint32_t bad = 0;
+        for (uint32_t k = tid; k < count; k += WEO_T) bad |= E.d_err[first + k] != 0 ? 1u : 0u;
+        if (bad) s_bad = 1u;
+        __syncthreads();
+    }
+    auto raw = [&]() {                                                 // the host transcoder's: the raw answers, as they are
+        for (uint32_t k = tid; k < count; k += WEO_T) {
+            const uint32_t i = first + k;
+            E.h_status[i] = E.d_status[i]; E.h_err[i] = E.d_err[i]; E.h_limit[i] = E.d_limit[i]; E.h_remaining[i] = E.d_remaining[i]; E.h_reset[i] = E.d_reset[i];
+        }
+        if (tid == 0) E.enc_len[r] = WIRE_ENC_RAW;
+    };
+    if (!one_piece && s_bad) { raw(); return; }
+    uint8_t* const dst = E.enc + wire_enco_off(first, r, A.item_max);
+    uint32_t carry = 0, flushed = 0;
+    for (uint32_t c0 = 0; c0 < count; c0 += WEO_P) {
+        const bool have = c0 + tid < count;
+        uint32_t st = 0, sl = 0, so = 0, body = 0, hdr = 0; uint64_t lim = 0, rem = 0, rst = 0;
+        if (have) {
+            const uint32_t i = first + c0 + tid;
+            st = E.d_status[i]; lim = (uint64_t)E.d_limit[i]; rem = (uint64_t)E.d_remaining[i]; rst = (uint64_t)E.d_reset[i];
+            const uint32_t ow = A.item_owner[i];
+            if (one_piece && E.d_err[i] != 0) s_bad = 1u;
+            if (ow != A.self && ow < nr) { sl = sfx_len[ow]; so = ow * WEO_SFX_STRIDE; }
+            body = (st ? 1u + wire_varint_len(st) : 0u) + (lim ? 1u + wire_varint_len(lim) : 0u) + (rem ? 1u + wire_varint_len(rem) : 0u) +
+                   (rst ? 1u + wire_varint_len(rst) : 0u) + sl;
+            hdr = body < 128u ? 2u : 3u;                               // 0x0a + the body's length: the size pass and the write pass both take it from here
+        }
+        const uint32_t mine = hdr + body;
+        const uint32_t incl = wire_wave_incl_scan(mine);
+        if (lane == 63u) wsum[wave] = incl;
+        __syncthreads();
+        if (one_piece && s_bad) { raw(); return; }
+        uint32_t base = carry + incl - mine, chunk = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < WEO_T / 64; ++w) { const uint32_t s = wsum[w]; if (w < wave) base += s; chunk += s; }
+        if (have) {
+            uint8_t* o = stage + base;
+            o[0] = 0x0a;
+            if (hdr == 2u) o[1] = (uint8_t)body; else { o[1] = (uint8_t)(body | 0x80u); o[2] = (uint8_t)(body >> 7); }
+            o += hdr;
+            if (st) o += wire_put_field(o, 0x08, st);
+            if (lim) o += wire_put_field(o, 0x10, lim);
+            if (rem) o += wire_put_field(o, 0x18, rem);
+            if (rst) o += wire_put_field(o, 0x20, rst);
+            for (uint32_t b = 0; b < sl; ++b) o[b] = sfx[so + b];
+        }
+        const uint32_t total = carry + chunk;
+        const bool last = c0 + WEO_P >= count;
+        const uint32_t full = last ? (total + 15u) & ~15u : total & ~15u;
+        if (last && tid < full - total) stage[total + tid] = 0;       // (the last word's padding: never read as part of the response)
+        __syncthreads();
+        for (uint32_t q = tid * 16u; q < full; q += WEO_T * 16u) *(uint4*)(dst + flushed + q) = *(const uint4*)(stage + q);
+        if (last) { if (tid == 0) E.enc_len[r] = flushed + total; return; }
+        uint8_t keep = 0;
+        if (tid < total - full) keep = stage[full + tid];
+        __syncthreads();
+        if (tid < total - full) stage[tid] = keep;
+        carry = total - full; flushed += full;
+        __syncthreads();
+    }
+}
+
 }  // namespace guber

@@ -202,13 +202,21 @@ static int mesh_front_pieces(guber_mesh* m, guber_front* f, const FrontGen& g, c
     return front_eval(f, gens.data(), res.data(), (uint32_t)gens.size(), &done);
 }
 
-static int mesh_eval(guber_mesh* m, const guber_batch_t* gens, const guber_mesh_rows_t* rows, guber_result_t* results) {
+// item_owner: NULL, or per rank NULL or n bytes on the rank's device — the ring's owner of every arrival item (k_mx_count's optional output)
+static int mesh_eval(guber_mesh* m, const guber_batch_t* gens, const guber_mesh_rows_t* rows, guber_result_t* results, uint8_t* const* item_owner = nullptr) {
     const uint32_t W = m->W;
     uint64_t total = 0;
     for (uint32_t r = 0; r < W; ++r) { m->ranks[r].n = gens[r].n; total += gens[r].n; clear_aggregates(results[r]); }
     m->st.calls++; m->st.requests += total;
     if (W == 1) {
         if (gens[0].n == 0) return 0;
+        if (item_owner && item_owner[0]) {
+            auto& R = m->ranks[0];
+            if (!rows || !rows[0].key_stride) return fail(GUBER_E_INVALID_ARG, "guber_mesh: the owner column is written for key rows");
+            HIPCHK(hipSetDevice(R.device));
+            hipLaunchKernelGGL(k_mx_owner_one, dim3((gens[0].n + 255u) / 256u), dim3(256), 0, R.st, gens[0].n, rows[0].key_len, rows[0].key_stride, R.f->max_key, item_owner[0]);
+            if (hipGetLastError() != hipSuccess) return fail(GUBER_E_HIP, "kernel launch");
+        }
         FrontGen g; g.b = gens[0];
         if (rows && rows[0].key_stride) { g.key_stride = rows[0].key_stride; g.key_len = rows[0].key_len; }   // (the front takes rows itself)
         return mesh_front_pieces(m, m->ranks[0].f, g, results[0]);
@@ -228,6 +236,7 @@ static int mesh_eval(guber_mesh* m, const guber_batch_t* gens, const guber_mesh_
             A.created_at = b.created_at; A.behavior = b.behavior; A.algorithm = b.algorithm;
             const bool in_rows = rows && rows[r].key_stride;         // (a rank's form is its own: each launches its own routing kernels)
             A.key_stride = in_rows ? rows[r].key_stride : 0u; A.key_len = in_rows ? rows[r].key_len : nullptr;
+            A.item_owner = item_owner ? item_owner[r] : nullptr;
             const uint32_t tiles = (b.n + FR_TILE - 1u) / FR_TILE;
             const size_t ring_bytes = m->ring_lds ? (size_t)m->npts * 8 : 0;
             if (in_rows) hipLaunchKernelGGL(k_mx_count<true>, dim3(tiles), dim3(FR_TILE), ring_bytes, R.st, A);
@@ -302,7 +311,7 @@ static int mesh_eval(guber_mesh* m, const guber_batch_t* gens, const guber_mesh_
 // rows[r].key_stride != 0: rank r's keys lie in ROWS (gens[r].key_bytes the first row, key_stride bytes apart, key_len[i] bytes of row i
 // are the key; gens[r].key_off NULL) — what the device wire decoder leaves; rows NULL or key_stride 0: packed.  Every check comes
 // before the first HIP call.
-extern "C" int guber_mesh_eval_rows_dev(guber_mesh_t* m, const guber_batch_t* gens, const guber_mesh_rows_t* rows, guber_result_t* results) {
+static int mesh_eval_rows_owner(guber_mesh_t* m, const guber_batch_t* gens, const guber_mesh_rows_t* rows, guber_result_t* results, uint8_t* const* item_owner) {
     if (!m || !gens || !results) return fail(GUBER_E_INVALID_ARG, "null argument");
     for (uint32_t r = 0; r < m->W; ++r) {
         int rc;
@@ -323,9 +332,13 @@ extern "C" int guber_mesh_eval_rows_dev(guber_mesh_t* m, const guber_batch_t* ge
     }
     std::lock_guard<std::mutex> lk(m->mu);
     const auto t0 = std::chrono::steady_clock::now();
-    const int rc = mesh_eval(m, gens, rows, results);
+    const int rc = mesh_eval(m, gens, rows, results, item_owner);
     m->st.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return rc;
+}
+
+extern "C" int guber_mesh_eval_rows_dev(guber_mesh_t* m, const guber_batch_t* gens, const guber_mesh_rows_t* rows, guber_result_t* results) {
+    return mesh_eval_rows_owner(m, gens, rows, results, nullptr);
 }
 
 extern "C" int guber_mesh_eval_dev(guber_mesh_t* m, const guber_batch_t* gens, guber_result_t* results) {

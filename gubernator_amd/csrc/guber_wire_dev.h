@@ -4,6 +4,15 @@
 #include "../../include/guber_wire.h"
 #include "guber_kernels_wire.h"
 
+// guber_wire_dev_eval_mesh_enc's buffers, made on a decoder's first such call
+struct WireMeshEnc {
+    DevBuf<uint8_t> d_owner, d_sfx; DevBuf<uint32_t> d_sfx_len;                            // k_mx_count's item_owner[]; the peers' suffixes and their lengths
+    PinBuf<uint8_t> h_sfx, h_owner;                                                        // staging of the table; item_owner[] read back
+    CohBuf<uint8_t> enc, res; CohBuf<uint32_t> enc_len;                                    // what k_wire_enc_owner writes in place: responses, raw answers
+    uint32_t host_rpcs = 0;                                                                // RPCs of the last call the host transcoder wrote (an item error)
+    void release() { d_owner.release(); d_sfx.release(); d_sfx_len.release(); h_sfx.release(); h_owner.release(); enc.release(); res.release(); enc_len.release(); }
+};
+
 struct guber_wire_dev {
     guber_engine* e = nullptr;
     uint32_t max_items = 0, max_bytes = 0, max_rpcs = 0, cap_per_rpc = 0, stride = 0;
@@ -23,6 +32,7 @@ struct guber_wire_dev {
     // the asynchronous calls (guber_wire_dev_*_async / _poll: the payload stage of guber_wire_pool.h): a stream of the caller's for the
     // decode, one event for "the decode's verdicts are in host memory", one for "the answers are where the caller wanted them"
     hipStream_t own = nullptr; hipEvent_t ev_dec = nullptr, ev_eval = nullptr; bool dec_pending = false, eval_pending = false, routed = false;
+    WireMeshEnc menc;
     hipStream_t stream() const { return own ? own : e->stream; }
 };
 
@@ -74,7 +84,7 @@ extern "C" void guber_wire_dev_destroy(guber_wire_dev_t* d) {
     if (d->ev_eval) (void)hipEventDestroy(d->ev_eval);
     d->h_buf.release(); d->h_rep.release(); d->d_buf.release(); d->d_rows.release(); d->d_u8.release();
     d->d_u32.release(); d->d_went.release(); d->d_rec.release(); d->d_status.release(); d->d_algo.release(); d->d_i64.release(); d->d_out64.release(); d->d_out8.release();
-    d->h_cols.release();
+    d->h_cols.release(); d->menc.release();
     delete d;
 }
 
@@ -334,8 +344,8 @@ extern "C" int guber_wire_dev_eval_front(guber_wire_dev_t* d, guber_front_t* f, 
 // per-item is_owner is not handed on (the ring decides), which is why a decode with a peer RPC in it is refused: its items are evaluated
 // where they arrive (gubernator.go:486) — guber_wire_dev_eval_front's job.  Pre-rejected items and dead slots have empty key rows: they
 // stay, keep their place and earn the front's item error.  Every refusal comes before anything is enqueued.
-extern "C" int guber_wire_dev_eval_mesh(guber_wire_dev_t* const* decs, guber_mesh_t* m, guber_result_t* results) {
-    if (!decs || !m || !results) return fail(GUBER_E_INVALID_ARG, "null argument");
+// the refusals guber_wire_dev_eval_mesh makes of its decoders; -> the call's now_ms
+static int wire_dev_mesh_check(guber_wire_dev_t* const* decs, guber_mesh_t* m, int64_t* now_out) {
     const uint32_t W = m->W;
     int64_t now_ms = 0; bool have_now = false;
     for (uint32_t r = 0; r < W; ++r) {
@@ -349,13 +359,15 @@ extern "C" int guber_wire_dev_eval_mesh(guber_wire_dev_t* const* decs, guber_mes
         if (d->n_items > m->max_n) return fail(GUBER_E_BATCH_TOO_LARGE, "more items than the mesh's generations hold");
         if (have_now && d->now_ms != now_ms) return fail(GUBER_E_INVALID_ARG, "guber_wire_dev_eval_mesh: the decodes of a call carry one now_ms");
         now_ms = d->now_ms; have_now = true;
-        const guber_result_t& q = results[r];
-        if (!q.status || !q.limit || !q.remaining || !q.reset_time || !q.err) return fail(GUBER_E_INVALID_ARG, "result is missing an array");
     }
-    std::vector<guber_batch_t> gens(W, guber_batch_t{}); std::vector<guber_mesh_rows_t> rows(W, guber_mesh_rows_t{}); std::vector<guber_result_t> dr(W, guber_result_t{});
+    *now_out = now_ms;
+    return GUBER_OK;
+}
+// ... and the generations of a call: every decoder's last decode as its rank's generation in rows, its answers into the decoder's own HBM columns
+static void wire_dev_mesh_gens(guber_wire_dev_t* const* decs, uint32_t W, int64_t now_ms, std::vector<guber_batch_t>& gens, std::vector<guber_mesh_rows_t>& rows,
+                               std::vector<guber_result_t>& dr) {
+    gens.assign(W, guber_batch_t{}); rows.assign(W, guber_mesh_rows_t{}); dr.assign(W, guber_result_t{});
     for (uint32_t r = 0; r < W; ++r) {
-        guber_result_t& q = results[r];
-        q.over_limit_count = q.cache_hits = q.cache_misses = q.unexpired_evictions = 0; q.cache_size = 0;
         gens[r].now_ms = now_ms;
         guber_wire_dev* d = decs[r];
         if (!d || !d->n_items) continue;
@@ -365,6 +377,23 @@ extern "C" int guber_wire_dev_eval_mesh(guber_wire_dev_t* const* decs, guber_mes
         rows[r].key_stride = g.key_stride; rows[r].key_len = g.key_len;
         const size_t M = d->max_items;
         dr[r].status = d->d_out8.p; dr[r].err = d->d_out8.p + M; dr[r].limit = d->d_out64.p; dr[r].remaining = d->d_out64.p + M; dr[r].reset_time = d->d_out64.p + 2 * M;
+    }
+}
+extern "C" int guber_wire_dev_eval_mesh(guber_wire_dev_t* const* decs, guber_mesh_t* m, guber_result_t* results) {
+    if (!decs || !m || !results) return fail(GUBER_E_INVALID_ARG, "null argument");
+    const uint32_t W = m->W;
+    int64_t now_ms = 0;
+    { const int rc = wire_dev_mesh_check(decs, m, &now_ms); if (rc) return rc; }
+    for (uint32_t r = 0; r < W; ++r) {
+        if (!decs[r] || !decs[r]->n_items) continue;
+        const guber_result_t& q = results[r];
+        if (!q.status || !q.limit || !q.remaining || !q.reset_time || !q.err) return fail(GUBER_E_INVALID_ARG, "result is missing an array");
+    }
+    std::vector<guber_batch_t> gens; std::vector<guber_mesh_rows_t> rows; std::vector<guber_result_t> dr;
+    wire_dev_mesh_gens(decs, W, now_ms, gens, rows, dr);
+    for (uint32_t r = 0; r < W; ++r) {
+        guber_result_t& q = results[r];
+        q.over_limit_count = q.cache_hits = q.cache_misses = q.unexpired_evictions = 0; q.cache_size = 0;
     }
     {   // (every decode was synchronised on its stream: guber_wire_dev_decode* read its verdicts back)
         const int rc = guber_mesh_eval_rows_dev(m, gens.data(), rows.data(), dr.data());
@@ -389,6 +418,148 @@ extern "C" int guber_wire_dev_eval_mesh(guber_wire_dev_t* const* decs, guber_mes
         HIPCHK(hipMemcpyAsync(q.remaining, d->d_out64.p + M, n * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(q.reset_time, d->d_out64.p + 2 * M, n * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
+    }
+    return GUBER_OK;
+}
+// ---- guber_wire_dev_eval_mesh_enc: the same, answered as serialized GetRateLimitsResp bytes with the owner's address (include/guber_wire.h) ----
+// the worst case of a decoder's last decode INCLUDING error texts: per item guber_wire_encode_bound's terms (tag, length, four varint
+// fields, the error field's header, wrapper texts, a message of at most 256 bytes) and the longest suffix, plus the keys an error text
+// may quote — name + "_" + unique_key of every item: no more than the payload bytes and one byte per item
+extern "C" size_t guber_wire_dev_mesh_enc_bound(const guber_wire_dev_t* d, const char* const* owner_addr, uint32_t n_ranks) {
+    const size_t longest = guber::wire::owner_suffix_longest(owner_addr, n_ranks, guber::WEO_RANKS);
+    if (!d || !longest || !d->n_items) return 0;
+    size_t payload = 0;
+    const uint32_t* h_len = d->h_meta() + d->max_rpcs;
+    for (uint32_t q = 0; q < d->nrpc; ++q) payload += h_len[q];
+    return (size_t)d->n_items * (guber::wire::RESP_ERR_ITEM_BOUND + 1 + longest) + payload;
+}
+extern "C" uint32_t guber_wire_dev_mesh_enc_piece(void) { return guber::WEO_P; }
+extern "C" uint32_t guber_wire_dev_mesh_enc_host_rpcs(const guber_wire_dev_t* d) { return d ? d->menc.host_rpcs : 0u; }
+// one RPC the device left raw: its payload once more through the host transcoder, the raw answers filled in, guber_wire_encode_responses_owner
+// (wb: made before anything was enqueued, large enough for the decode's largest RPC)
+static int wire_mesh_enc_host_rpc(guber_wire_dev* d, guber_wire_batch_t* wb, uint32_t q, uint32_t first, uint32_t count, const guber_result_t& raw, const uint8_t* owner, uint32_t self,
+                                  const char* const* owner_addr, uint32_t n_ranks, int wrap_errors, uint8_t* out, size_t cap, size_t* used) {
+    const uint32_t* h_off = d->h_meta(); const uint32_t* h_len = h_off + d->max_rpcs;
+    guber_wire_batch_reset(wb, d->now_ms);
+    uint32_t f0 = 0, c0 = 0;
+    int rc = guber_wire_decode_requests(wb, d->h_pay() + h_off[q], h_len[q], 0, 1, &f0, &c0);
+    if (!rc && c0 != count) rc = GUBER_E_HIP;
+    if (rc) return fail(GUBER_E_HIP, "guber_wire_dev_eval_mesh_enc: the device's and the host's decoders disagree about a payload");
+    guber_result_t* hr = guber_wire_batch_result(wb);
+    memcpy(hr->status, raw.status + first, count); memcpy(hr->err, raw.err + first, count);
+    memcpy(hr->limit, raw.limit + first, (size_t)count * 8); memcpy(hr->remaining, raw.remaining + first, (size_t)count * 8);
+    memcpy(hr->reset_time, raw.reset_time + first, (size_t)count * 8);
+    rc = guber_wire_encode_responses_owner(wb, 0, count, wrap_errors, owner + first, self, owner_addr, n_ranks, out, cap, used);
+    if (rc) return fail(rc, "guber_wire_dev_eval_mesh_enc: an RPC's responses did not fit the bound");
+    return GUBER_OK;
+}
+extern "C" int guber_wire_dev_eval_mesh_enc(guber_wire_dev_t* const* decs, guber_mesh_t* m, const char* const* owner_addr, int wrap_errors, guber_wire_mesh_resp_t* out) {
+    if (!decs || !m || !owner_addr || !out) return fail(GUBER_E_INVALID_ARG, "null argument");
+    const uint32_t W = m->W;
+    int64_t now_ms = 0;
+    { const int rc = wire_dev_mesh_check(decs, m, &now_ms); if (rc) return rc; }
+    const size_t longest = guber::wire::owner_suffix_longest(owner_addr, W, guber::WEO_RANKS);
+    if (!longest) return fail(GUBER_E_INVALID_ARG, "guber_wire_dev_eval_mesh_enc: every rank has an address of 1 .. GUBER_WIRE_OWNER_ADDR_MAX bytes");
+    for (uint32_t r = 0; r < W; ++r) {
+        guber_wire_dev* d = decs[r];
+        if (!d || !d->nrpc) continue;
+        if (!out[r].off || !out[r].len || (d->n_items && (!out[r].buf))) return fail(GUBER_E_INVALID_ARG, "guber_wire_dev_eval_mesh_enc: a rank's response arrays are missing");
+        if (out[r].cap < guber_wire_dev_mesh_enc_bound(d, owner_addr, W)) return fail(GUBER_E_NOMEM, "response buffer below guber_wire_dev_mesh_enc_bound()");
+    }
+    // the peers' suffixes, once per call; no item of the call takes more than item_max bytes
+    const uint32_t item_max = 1u + 2u + guber::wire::RESP_BODY_MAX + (uint32_t)longest;
+    std::vector<uint8_t> sfx((size_t)guber::WEO_RANKS * guber::WEO_SFX_STRIDE, 0); std::vector<uint32_t> sfx_len(guber::WEO_RANKS, 0);
+    for (uint32_t p = 0; p < W; ++p) sfx_len[p] = guber::wire::put_owner_suffix(sfx.data() + (size_t)p * guber::WEO_SFX_STRIDE, owner_addr[p], (uint32_t)strlen(owner_addr[p]));
+    for (uint32_t r = 0; r < W; ++r) if (decs[r]) decs[r]->menc.host_rpcs = 0;
+    // the host transcoder's batch for the RPCs the device leaves raw: one, for the largest RPC of the call, before anything is enqueued
+    struct HostBatch { guber_wire_batch_t* p = nullptr; ~HostBatch() { guber_wire_batch_destroy(p); } } hb;
+    {
+        uint32_t most = 1; size_t longest_rpc = 0;
+        for (uint32_t r = 0; r < W; ++r) {
+            guber_wire_dev* d = decs[r];
+            if (!d || !d->n_items) continue;
+            const uint32_t* h_len = d->h_meta() + d->max_rpcs;
+            for (uint32_t q = 0; q < d->nrpc; ++q) {
+                if (d->out.rep_status[q] != GUBER_OK) continue;
+                most = std::max(most, (uint32_t)d->out.rep_count[q]); longest_rpc = std::max<size_t>(longest_rpc, h_len[q]);
+            }
+        }
+        if (guber_wire_batch_create(most, (uint32_t)std::min<size_t>(longest_rpc + most + 16, 0xffffffffu), 0, &hb.p)) return fail(GUBER_E_NOMEM, "guber_wire_dev_eval_mesh_enc: no memory for the host transcoder's batch");
+    }
+    std::vector<WireMeshEnc*> X(W, nullptr); std::vector<guber_result_t> raw(W, guber_result_t{});
+    for (uint32_t r = 0; r < W; ++r) {                                                      // (allocations: nothing is enqueued yet)
+        guber_wire_dev* d = decs[r];
+        if (!d || !d->n_items) continue;
+        std::lock_guard<std::mutex> lk(d->e->mu);
+        if (d->e->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
+        WireMeshEnc* x = X[r] = &d->menc;
+        const size_t M = d->max_items, col8 = (M + 63) & ~(size_t)63;
+        if (x->d_owner.ensure(M) || x->d_sfx.ensure(sfx.size()) || x->d_sfx_len.ensure(guber::WEO_RANKS) || x->h_sfx.ensure(sfx.size() + 4 * guber::WEO_RANKS) ||
+            x->h_owner.ensure(M) || x->enc.ensure(guber::wire_enco_bytes(d->n_items, d->nrpc, item_max)) || x->res.ensure(2 * col8 + 3 * 8 * M + 64) ||
+            x->enc_len.ensure(d->max_rpcs)) return GUBER_E_NOMEM;
+        uint8_t* q = x->res.p;
+        raw[r].status = q; q += col8; raw[r].err = q; q += col8;
+        raw[r].limit = (int64_t*)q; q += 8 * M; raw[r].remaining = (int64_t*)q; q += 8 * M; raw[r].reset_time = (int64_t*)q;
+    }
+    std::vector<guber_batch_t> gens; std::vector<guber_mesh_rows_t> rows; std::vector<guber_result_t> dr;
+    wire_dev_mesh_gens(decs, W, now_ms, gens, rows, dr);
+    std::vector<uint8_t*> item_owner(W, nullptr);
+    for (uint32_t r = 0; r < W; ++r) if (X[r]) item_owner[r] = X[r]->d_owner.p;
+    { const int rc = mesh_eval_rows_owner(m, gens.data(), rows.data(), dr.data(), item_owner.data()); if (rc) return rc; }
+    { const int rc = guber_mesh_synchronize(m); if (rc) return rc; }
+    // the encoder, once per rank, behind the mesh's last hop; then the bytes, RPC by RPC
+    for (uint32_t r = 0; r < W; ++r) {
+        guber_wire_dev* d = decs[r];
+        if (!d || !d->n_items) continue;
+        WireMeshEnc* x = X[r];
+        guber_engine* e = d->e;
+        std::lock_guard<std::mutex> lk(e->mu);
+        if (e->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
+        hipStream_t st = d->stream();
+        memcpy(x->h_sfx.p, sfx.data(), sfx.size()); memcpy(x->h_sfx.p + sfx.size(), sfx_len.data(), 4 * guber::WEO_RANKS);
+        HIPCHK(hipMemcpyAsync(x->d_sfx.p, x->h_sfx.p, sfx.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(x->d_sfx_len.p, x->h_sfx.p + sfx.size(), 4 * guber::WEO_RANKS, hipMemcpyHostToDevice, st));
+        guber::WireEncOwner A{};
+        guber::WireEnc& E = A.E;
+        E.nrpc = d->nrpc; E.first = d->sc.first; E.count = d->sc.count; E.status = d->sc.status;
+        E.d_status = dr[r].status; E.d_err = dr[r].err; E.d_limit = dr[r].limit; E.d_remaining = dr[r].remaining; E.d_reset = dr[r].reset_time;
+        E.enc = x->enc.p; E.enc_len = x->enc_len.p;
+        E.h_status = raw[r].status; E.h_err = raw[r].err; E.h_limit = raw[r].limit; E.h_remaining = raw[r].remaining; E.h_reset = raw[r].reset_time;
+        A.item_owner = x->d_owner.p; A.self = r; A.n_ranks = W; A.item_max = item_max; A.sfx = x->d_sfx.p; A.sfx_len = x->d_sfx_len.p;
+        hipLaunchKernelGGL(guber::k_wire_enc_owner, dim3(d->nrpc), dim3(guber::WEO_T), 0, st, A);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(x->h_owner.p, x->d_owner.p, d->n_items, hipMemcpyDeviceToHost, st));
+    }
+    for (uint32_t r = 0; r < W; ++r) {
+        guber_wire_dev* d = decs[r];
+        if (!d || !d->nrpc) continue;
+        guber_wire_mesh_resp_t& o = out[r];
+        if (!d->n_items) { for (uint32_t q = 0; q < d->nrpc; ++q) { o.off[q] = 0; o.len[q] = 0; } continue; }
+        WireMeshEnc* x = X[r];
+        {
+            std::lock_guard<std::mutex> lk(d->e->mu);
+            if (d->e->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
+            HIPCHK(hipStreamSynchronize(d->stream()));
+        }
+        const volatile uint32_t* h_first = d->out.rep_first; const volatile uint32_t* h_count = d->out.rep_count; const volatile int32_t* h_status = d->out.rep_status;
+        if (o.owner_rank) memcpy(o.owner_rank, x->h_owner.p, d->n_items);
+        size_t at = 0;
+        for (uint32_t q = 0; q < d->nrpc; ++q) {
+            const uint32_t first = h_first[q], count = h_status[q] == GUBER_OK ? h_count[q] : 0u;
+            o.off[q] = (uint32_t)at; o.len[q] = 0;
+            if (!count) continue;
+            const uint32_t el = x->enc_len.p[q];
+            size_t used = 0;
+            if (el != guber::WIRE_ENC_RAW) {
+                if (el > o.cap - at) return fail(GUBER_E_HIP, "guber_wire_dev_eval_mesh_enc: the device's responses exceed the bound");
+                memcpy(o.buf + at, x->enc.p + guber::wire_enco_off(first, q, item_max), el); used = el;
+            } else {
+                const int rc = wire_mesh_enc_host_rpc(d, hb.p, q, first, count, raw[r], x->h_owner.p, r, owner_addr, W, wrap_errors, o.buf + at, o.cap - at, &used);
+                if (rc) return rc;
+                x->host_rpcs++;
+            }
+            o.len[q] = (uint32_t)used; at += used;
+        }
     }
     return GUBER_OK;
 }

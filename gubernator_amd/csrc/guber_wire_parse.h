@@ -150,6 +150,46 @@ GW_HD bool parse_req(const uint8_t* p, const uint8_t* end, ReqFields& f) {
     return true;
 }
 
+// ---- RateLimitResp.metadata{"owner": <the owner's GRPCAddress>} (gubernator.go:267-268, :379-381): field 6, ONE map entry —
+//   32 <varint entry_len> 0a 05 "owner" 12 <varint addr_len> <addr>
+// a constant per peer, written behind field 5 (the order both protobuf runtimes write).  One builder for the host transcoder
+// (wire.cpp) and for the table the device encoder copies from (k_wire_enc_owner): the bytes and their number have one source.
+constexpr uint32_t varint_len_c(uint64_t v) { return v < 0x80ull ? 1u : 1u + varint_len_c(v >> 7); }
+constexpr uint32_t OWNER_ADDR_MAX = 264;                            // = GUBER_WIRE_OWNER_ADDR_MAX: a 253-byte host name, ':', five digits, rounded up to 8
+constexpr uint32_t OWNER_KEY_LEN = 5;                               // "owner"
+constexpr uint32_t owner_entry_len(uint32_t addr) { return 1u + 1u + OWNER_KEY_LEN + 1u + varint_len_c(addr) + addr; }
+constexpr uint32_t owner_suffix_len(uint32_t addr) { return 1u + varint_len_c(owner_entry_len(addr)) + owner_entry_len(addr); }
+constexpr uint32_t OWNER_SUFFIX_MAX = owner_suffix_len(OWNER_ADDR_MAX);
+constexpr uint32_t RESP_BODY_MAX = 2u + 3u * 11u;                   // status (tag + one byte), three int64 fields (tag + ten bytes)
+constexpr uint32_t RESP_OWNER_BODY_MAX = RESP_BODY_MAX + OWNER_SUFFIX_MAX;
+constexpr uint32_t RESP_OWNER_ITEM_MAX = 1u + varint_len_c(RESP_OWNER_BODY_MAX) + RESP_OWNER_BODY_MAX;   // an item without an error, at most
+static_assert(OWNER_SUFFIX_MAX == 277 && RESP_OWNER_BODY_MAX == 312 && RESP_OWNER_ITEM_MAX == 315, "include/guber_wire.h states these");
+// what one answer takes at most WITH an error text (guber_wire_encode_bound's terms, beside the key the text may quote): tag + length (<= 4),
+// four varint fields (<= 11 each), the error field's header (<= 3), wrapper texts (<= 40) and a message of at most 256 bytes
+constexpr size_t RESP_ERR_ITEM_BOUND = 4 + 44 + 3 + 40 + 256;
+// the addresses of a call: all there, none empty, none above OWNER_ADDR_MAX, at most max_ranks of them; -> the longest suffix (0: refused)
+inline size_t owner_suffix_longest(const char* const* owner_addr, uint32_t n_ranks, uint32_t max_ranks) {
+    if (!owner_addr || n_ranks == 0 || n_ranks > max_ranks) return 0;
+    size_t longest = 0;
+    for (uint32_t r = 0; r < n_ranks; ++r) {
+        const size_t n = owner_addr[r] ? strnlen(owner_addr[r], OWNER_ADDR_MAX + 1) : 0;
+        if (n == 0 || n > OWNER_ADDR_MAX) return 0;
+        const size_t sl = owner_suffix_len((uint32_t)n);
+        if (sl > longest) longest = sl;
+    }
+    return longest;
+}
+// out: owner_suffix_len(n) bytes; 1 <= n <= OWNER_ADDR_MAX (lengths of one or two varint bytes)
+inline uint32_t put_owner_suffix(uint8_t* out, const char* addr, uint32_t n) {
+    uint8_t* p = out;
+    auto put = [&](uint32_t v) { while (v >= 0x80u) { *p++ = (uint8_t)(v | 0x80u); v >>= 7; } *p++ = (uint8_t)v; };
+    *p++ = 0x32; put(owner_entry_len(n));
+    *p++ = 0x0a; *p++ = (uint8_t)OWNER_KEY_LEN; memcpy(p, "owner", OWNER_KEY_LEN); p += OWNER_KEY_LEN;
+    *p++ = 0x12; put(n);
+    memcpy(p, addr, n); p += n;
+    return (uint32_t)(p - out);
+}
+
 }}  // namespace guber::wire
 
 // ---- the payload stage's item bound (host only: guber_wire_pool.h's callers, before their RPC joins a stage; here so that the wire fuzz

@@ -11,6 +11,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <new>
 #include <string>
 #include <vector>
@@ -241,20 +242,38 @@ extern "C" size_t guber_wire_encode_bound(const guber_wire_batch_t* b, uint32_t 
     // tag + length (<= 3) + 4 varint fields (<= 11 each) + error field: wrapper text + key + message (<= 256).  (The peer RPC's wrappers,
     // 82 bytes and no key, around a message of at most 92 lie inside the 40 + 256 as well.)
     size_t bound = 0;
-    for (uint32_t i = first; i < first + count; ++i) bound += 4 + 44 + 3 + 40 + 256 + (b->key_off[i + 1] - b->key_off[i]);
+    for (uint32_t i = first; i < first + count; ++i) bound += RESP_ERR_ITEM_BOUND + (b->key_off[i + 1] - b->key_off[i]);
     return bound;
 }
 
 namespace {
-int encode_responses(const guber_wire_batch_t* b, uint32_t first, uint32_t count, int wrap_errors, uint8_t* out, size_t cap, size_t* len) {
+// the owner's address on the answers that were not evaluated as the arrival instance's own (include/guber_wire.h, guber_wire_encode_responses_owner)
+struct OwnerCtx {
+    const uint8_t* owner_rank; uint32_t self_rank, n_ranks;
+    const uint8_t* const* suffix; const uint32_t* suffix_len;          // per rank: wire::put_owner_suffix
+};
+int encode_responses(const guber_wire_batch_t* b, uint32_t first, uint32_t count, int wrap_errors, uint8_t* out, size_t cap, size_t* len, const OwnerCtx* oc = nullptr) {
     if (!b || !len || (!out && cap) || first > b->n || count > b->n - first) return GUBER_E_INVALID_ARG;
     size_t used = 0;
     bool overflow = false;
     for (uint32_t i = first; i < first + count; ++i) {
+        const bool has_err = b->pre_err[i] != GUBER_WIRE_PRE_OK || b->r_err[i] != GUBER_ITEM_OK;
+        // whose answer this is: pre-rejected items, dead slots and keys the ring cannot place never left the arrival instance's validation
+        uint32_t owner = oc ? oc->self_rank : 0;
+        if (oc && b->pre_err[i] == GUBER_WIRE_PRE_OK && oc->owner_rank[i - first] != 0xffu) owner = oc->owner_rank[i - first];
+        const bool remote = oc && owner != oc->self_rank;
         std::string err;
-        if (b->pre_err[i] != GUBER_WIRE_PRE_OK || b->r_err[i] != GUBER_ITEM_OK) err = item_error(b, i, wrap_errors);
+        if (has_err) {
+            if (!remote) err = item_error(b, i, wrap_errors);
+            else if (!(b->behavior[i] & GUBER_BEHAVIOR_GLOBAL)) err = item_error(b, i, ERR_PEER);   // forwarded: the owner's GetPeerRateLimits text, handed on unchanged (asyncRequest)
+            else {                                                                                   // a non-owner's replica: gubernator.go:261 around :416 around :600
+                static const char kLocal[] = "Error in getLocalRateLimit: ";
+                err = "Error in getGlobalRateLimit: during in getLocalRateLimit: " + item_error(b, i, ERR_PEER).substr(sizeof kLocal - 1);
+            }
+        }
         const RespFields f = resp_fields(b, i, !err.empty());
-        const size_t body = resp_body_size(f, err.size());
+        const size_t sfx = remote ? oc->suffix_len[owner] : 0;
+        const size_t body = resp_body_size(f, err.size()) + sfx;
         const size_t total = 1 + varint_size(body) + body;
         if (!overflow && used + total <= cap) {
             uint8_t* p = out + used;
@@ -265,6 +284,7 @@ int encode_responses(const guber_wire_batch_t* b, uint32_t first, uint32_t count
             if (f.remaining) { *p++ = 0x18; p = put_varint(p, f.remaining); }
             if (f.reset) { *p++ = 0x20; p = put_varint(p, f.reset); }
             if (!err.empty()) { *p++ = 0x2a; p = put_varint(p, err.size()); memcpy(p, err.data(), err.size()); p += err.size(); }
+            if (sfx) { memcpy(p, oc->suffix[owner], sfx); p += sfx; }   // field 6: behind field 5, as both runtimes write it
         } else {
             overflow = true;
         }
@@ -274,6 +294,24 @@ int encode_responses(const guber_wire_batch_t* b, uint32_t first, uint32_t count
     return overflow ? GUBER_E_NOMEM : GUBER_OK;
 }
 }  // namespace
+
+extern "C" size_t guber_wire_encode_bound_owner(const guber_wire_batch_t* b, uint32_t first, uint32_t count, const char* const* owner_addr, uint32_t n_ranks) {
+    const size_t longest = owner_suffix_longest(owner_addr, n_ranks, 255);
+    if (!b || first > b->n || count > b->n - first || !longest) return 0;
+    return guber_wire_encode_bound(b, first, count) + (size_t)count * longest;   // (the texts of a forwarded and of a GLOBAL non-owner item lie inside the 40 + 256 as well)
+}
+extern "C" int guber_wire_encode_responses_owner(const guber_wire_batch_t* b, uint32_t first, uint32_t count, int wrap_errors, const uint8_t* owner_rank,
+                                                 uint32_t self_rank, const char* const* owner_addr, uint32_t n_ranks, uint8_t* out, size_t cap, size_t* len) {
+    if (!owner_suffix_longest(owner_addr, n_ranks, 255) || self_rank >= n_ranks || (count && !owner_rank)) return GUBER_E_INVALID_ARG;
+    for (uint32_t k = 0; k < count; ++k) if (owner_rank[k] != 0xffu && owner_rank[k] >= n_ranks) return GUBER_E_INVALID_ARG;
+    std::vector<uint8_t> bytes((size_t)n_ranks * OWNER_SUFFIX_MAX); std::vector<const uint8_t*> sfx(n_ranks); std::vector<uint32_t> sl(n_ranks);
+    for (uint32_t r = 0; r < n_ranks; ++r) {
+        sfx[r] = bytes.data() + (size_t)r * OWNER_SUFFIX_MAX;
+        sl[r] = put_owner_suffix(bytes.data() + (size_t)r * OWNER_SUFFIX_MAX, owner_addr[r], (uint32_t)strlen(owner_addr[r]));
+    }
+    const OwnerCtx oc{owner_rank, self_rank, n_ranks, sfx.data(), sl.data()};
+    return encode_responses(b, first, count, wrap_errors ? ERR_CLIENT : ERR_BARE, out, cap, len, &oc);
+}
 
 extern "C" int guber_wire_encode_responses(const guber_wire_batch_t* b, uint32_t first, uint32_t count, int wrap_errors,
                                            uint8_t* out, size_t cap, size_t* len) {

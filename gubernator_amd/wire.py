@@ -14,6 +14,7 @@ WIRE_SYMBOLS = [
     "guber_wire_batch_create", "guber_wire_batch_destroy", "guber_wire_batch_reset", "guber_wire_batch_size",
     "guber_wire_decode_requests", "guber_wire_decode_peer_requests", "guber_wire_batch_view", "guber_wire_batch_result", "guber_wire_batch_pre_errors",
     "guber_wire_eval", "guber_wire_encode_bound", "guber_wire_encode_responses", "guber_wire_encode_peer_responses",
+    "guber_wire_encode_bound_owner", "guber_wire_encode_responses_owner", "guber_wire_dev_mesh_enc_bound", "guber_wire_dev_eval_mesh_enc", "guber_wire_dev_mesh_enc_host_rpcs", "guber_wire_dev_mesh_enc_piece",
     "guber_wire_items_create", "guber_wire_items_destroy", "guber_wire_decode_globals", "guber_wire_encode_globals",
     "guber_wire_dev_create", "guber_wire_dev_destroy", "guber_wire_dev_decode", "guber_wire_dev_buffer", "guber_wire_dev_decode_staged",
     "guber_wire_dev_eval", "guber_wire_dev_eval_front", "guber_wire_dev_eval_mesh", "guber_wire_dev_columns",
@@ -53,6 +54,10 @@ def _lib():
         L.guber_wire_encode_bound.restype = C.c_size_t
         L.guber_wire_encode_responses.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t,
                                                   C.POINTER(C.c_size_t)]
+        L.guber_wire_encode_bound_owner.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32]
+        L.guber_wire_encode_bound_owner.restype = C.c_size_t
+        L.guber_wire_encode_responses_owner.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32,
+                                                        C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.guber_wire_items_create.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
         L.guber_wire_items_destroy.argtypes = [C.c_void_p]
         L.guber_wire_items_destroy.restype = None
@@ -148,6 +153,26 @@ class WireBatch:
         return bytes(buf[:n.value])
 
 
+    def encode_owner(self, first, count, owner_rank, self_rank, owner_addr, wrap_errors=True, cap=None):
+        """guber_wire_encode_responses_owner: the responses of [first, first + count) with metadata{"owner": owner_addr[owner_rank[k]]} on
+        every answer another rank owns (owner_rank: uint8 per item, 0xFF = none; owner_addr: bytes or str per rank).  cap None: the bound
+        (guber_wire_encode_bound_owner).  -> bytes; GuberError (with .needed = the size wanted when the buffer was too small)"""
+        addrs = [a.encode() if isinstance(a, str) else a for a in owner_addr]
+        arr = (C.c_char_p * max(len(addrs), 1))(*addrs)
+        own = np.ascontiguousarray(owner_rank, np.uint8)
+        if cap is None:
+            cap = self.L.guber_wire_encode_bound_owner(self.h, first, count, arr, len(addrs))
+        buf = (C.c_uint8 * max(cap, 1))()
+        n = C.c_size_t()
+        rc = self.L.guber_wire_encode_responses_owner(self.h, first, count, 1 if wrap_errors else 0, own.ctypes.data if len(own) else None, self_rank,
+                                                      arr, len(addrs), buf, cap, C.byref(n))
+        if rc:
+            e = GuberError(rc, self.L.guber_strerror(rc).decode())
+            e.needed = n.value
+            raise e
+        return bytes(buf[:n.value])
+
+
 class WireItems:
     """UpdatePeerGlobalsReq payload -> the CacheItems the receiver installs (gubernator.go:425-459), ready for guber_add_items."""
 
@@ -236,7 +261,7 @@ class DevWireDecoder:
                                           status.ctypes.data, first.ctypes.data, count.ctypes.data, C.byref(items))
         if rc:
             raise GuberError(rc, lib().guber_last_error().decode())
-        self.n = items.value
+        self.n, self.nrpc = items.value, n
         return status[:n], first[:n], count[:n], items.value
 
     def buffer(self):
@@ -258,7 +283,7 @@ class DevWireDecoder:
                                                  now_ms, status.ctypes.data, first.ctypes.data, count.ctypes.data, C.byref(items))
         if rc:
             raise GuberError(rc, lib().guber_last_error().decode())
-        self.n = items.value
+        self.n, self.nrpc = items.value, n
         return status[:n], first[:n], count[:n], items.value
 
     def eval(self):
@@ -316,6 +341,65 @@ def eval_mesh(decoders, mesh):
     if rc:
         raise GuberError(rc, lib().guber_last_error().decode())
     return out
+
+
+def mesh_enc_piece():
+    """the items k_wire_enc_owner encodes per piece (diagnostic: the tests' RPC sizes stand around it)"""
+    L = _lib()
+    L.guber_wire_dev_mesh_enc_piece.restype = C.c_uint32
+    return L.guber_wire_dev_mesh_enc_piece()
+
+
+def mesh_enc_host_rpcs(decoder):
+    """RPCs of the decoder's last eval_mesh_enc that the host transcoder wrote (an item error); the device encoded the others"""
+    L = _lib()
+    L.guber_wire_dev_mesh_enc_host_rpcs.argtypes = [C.c_void_p]
+    L.guber_wire_dev_mesh_enc_host_rpcs.restype = C.c_uint32
+    return L.guber_wire_dev_mesh_enc_host_rpcs(decoder.h)
+
+
+class MeshResp(C.Structure):
+    """guber_wire_mesh_resp_t"""
+    _fields_ = [("buf", C.c_void_p), ("cap", C.c_size_t), ("off", C.c_void_p), ("len", C.c_void_p), ("owner_rank", C.c_void_p)]
+
+
+def mesh_enc_bound(decoder, owner_addr):
+    """guber_wire_dev_mesh_enc_bound: the bytes rank's responses take at most, error texts included, for the decoder's last decode"""
+    L = _lib()
+    L.guber_wire_dev_mesh_enc_bound.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32]
+    L.guber_wire_dev_mesh_enc_bound.restype = C.c_size_t
+    addrs = [a.encode() if isinstance(a, str) else a for a in owner_addr]
+    return L.guber_wire_dev_mesh_enc_bound(decoder.h, (C.c_char_p * max(len(addrs), 1))(*addrs), len(addrs))
+
+
+def _addr_array(owner_addr):
+    addrs = [a.encode() if isinstance(a, str) else a for a in owner_addr]
+    return addrs, (C.c_char_p * max(len(addrs), 1))(*addrs)
+
+
+def eval_mesh_enc(decoders, mesh, owner_addr, wrap_errors=True):
+    """guber_wire_dev_eval_mesh_enc: as eval_mesh, answered as serialized GetRateLimitsResp bytes — encoded on the device — with
+    metadata{"owner": owner_addr[p]} on every answer that rank p, not the arrival rank, owns.  owner_addr[p]: the name peer p has in the
+    ring.  -> per rank (responses, owner_rank): the list of response bytes, one per RPC of the rank's last decode (b"" for an RPC the
+    decode turned away), and the ring's owner per item (uint8, 0xFF = none); ([], empty) for a rank without a decoder"""
+    L = _lib()
+    L.guber_wire_dev_eval_mesh_enc.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(MeshResp)]
+    W = len(decoders)
+    addrs, arr = _addr_array(owner_addr)
+    decs = (C.c_void_p * max(W, 1))(*[d.h if d is not None else None for d in decoders])
+    out = (MeshResp * max(W, 1))()
+    keep = []
+    for r, d in enumerate(decoders):
+        nrpc, n = (getattr(d, "nrpc", 0), getattr(d, "n", 0)) if d is not None else (0, 0)
+        cap = mesh_enc_bound(d, addrs) if d is not None and len(addrs) == W else 0
+        buf = np.zeros(max(cap, 1), np.uint8)
+        off, ln, own = np.zeros(max(nrpc, 1), np.uint32), np.zeros(max(nrpc, 1), np.uint32), np.full(max(n, 1), 0xFF, np.uint8)
+        out[r] = MeshResp(buf.ctypes.data, cap, off.ctypes.data, ln.ctypes.data, own.ctypes.data)
+        keep.append((buf, off, ln, own, nrpc, n))
+    rc = L.guber_wire_dev_eval_mesh_enc(decs, mesh.h, arr if len(addrs) == W else None, 1 if wrap_errors else 0, out)
+    if rc:
+        raise GuberError(rc, lib().guber_last_error().decode())
+    return [([bytes(buf[int(off[q]):int(off[q]) + int(ln[q])]) for q in range(nrpc)], own[:n].copy()) for buf, off, ln, own, nrpc, n in keep]
 
 
 class WirePoolConfig(C.Structure):

@@ -16,7 +16,8 @@
  *                  algorithm 6, behavior 7 (enum varint), burst 8 (int64 varint),
  *                  metadata 9 (map entry, skipped: tracing propagation only), created_at 10 (optional int64)
  *   RateLimitResp: status 1 (enum), limit 2, remaining 3, reset_time 4 (int64), error 5 (string),
- *                  metadata 6 (never set on this path)
+ *                  metadata 6 (one entry, "owner" -> the owning peer's address, on the answers that were not evaluated as the
+ *                  arrival instance's own: guber_wire_encode_responses_owner, guber_wire_dev_eval_mesh_enc; no other entry is ever set)
  * Unknown fields are skipped by wire type, the last occurrence of a singular field wins, zero-valued
  * response fields are omitted and fields are written in field-number order — the bytes equal what the
  * protobuf runtimes produce for the same message.
@@ -107,6 +108,32 @@ int guber_wire_encode_responses(const guber_wire_batch_t* b, uint32_t first, uin
  * errors (table full, key too long), which the reference does not have, get the two outer wrappers.  guber_wire_encode_bound covers it. */
 int guber_wire_encode_peer_responses(const guber_wire_batch_t* b, uint32_t first, uint32_t count, uint8_t* out, size_t cap, size_t* len);
 
+/* Responses with the OWNER'S ADDRESS: guber_wire_encode_responses for an instance of a cluster.  The reference puts
+ * metadata{"owner": <owner's GRPCAddress>} on every answer that was not evaluated as the arrival instance's own: forwarded items
+ * (gubernator.go:379-381) and Behavior_GLOBAL items answered from a non-owner's replica (:267-268).
+ *   owner_rank[k]  the ring's owner of item first + k (a peer index below n_ranks; 0xFF = none: a key the ring cannot place) — what
+ *                  guber_ring_route or guber_wire_dev_eval_mesh_enc's owner_rank gives
+ *   self_rank      the instance the payload arrived at;  owner_addr[p]: the name peer p was given in guber_ring_create
+ * Per item, in this order:
+ *   1  pre-rejected (empty unique_key / name), a dead slot, or owner_rank 0xFF   error text as guber_wire_encode_responses, no metadata
+ *   2  owner_rank == self_rank                                                   as guber_wire_encode_responses (wrap_errors honoured), no metadata
+ *   3  a plain item of another owner (forwarded)        error text exactly guber_wire_encode_peer_responses' (gubernator.go:523 around :600:
+ *                                                       the owner's GetPeerRateLimits produced it, asyncRequest hands it on), metadata
+ *   4  Behavior_GLOBAL, another owner                   "Error in getGlobalRateLimit: during in getLocalRateLimit: " + what the peer text has
+ *                                                       behind "Error in getLocalRateLimit: " (gubernator.go:261, :416, :600), metadata
+ * An answer with an error carries the error (field 5) and the metadata (field 6) and no other field.  Field 6 is one map entry,
+ *   32 <varint entry_len> 0a 05 "owner" 12 <varint addr_len> <addr>
+ * behind field 5.  An address has 1 .. GUBER_WIRE_OWNER_ADDR_MAX bytes (a 253-byte host name, ':', five digits, rounded up to 8): entry_len and
+ * addr_len take two bytes from 128 on, a suffix is at most 277 bytes, a body without an error at most 35 + 277 = 312 — its length prefix two
+ * bytes from 128 on — and such an item at most 315.  GUBER_E_INVALID_ARG: a NULL, empty or over-long address, self_rank or an owner_rank
+ * outside the ranks.  guber_wire_encode_bound_owner = guber_wire_encode_bound + the longest suffix per item (0: refused arguments). */
+#define GUBER_WIRE_OWNER_ADDR_MAX 264
+size_t guber_wire_encode_bound_owner(const guber_wire_batch_t* b, uint32_t first, uint32_t count, const char* const* owner_addr, uint32_t n_ranks);
+int guber_wire_encode_responses_owner(const guber_wire_batch_t* b, uint32_t first, uint32_t count, int wrap_errors,
+                                      const uint8_t* owner_rank /* [count], 0xFF = none */, uint32_t self_rank,
+                                      const char* const* owner_addr, uint32_t n_ranks,
+                                      uint8_t* out, size_t cap, size_t* len);
+
 /* ---- UpdatePeerGlobals (peers.proto:51-63; sender global.go:234-283 broadcastPeers, receiver gubernator.go:425-459) ----
  * The third payload kind that touches the path: the owner of GLOBAL keys broadcasts their state, every other peer
  * installs it in its cache.
@@ -153,6 +180,8 @@ int guber_wire_encode_globals(const uint8_t* key_bytes, const uint32_t* key_off,
  *   guber_wire_dev_eval_mesh   the last decodes of one decoder per rank through a mesh of fronts (include/guber_gpu.h guber_mesh_*): every
  *                           item is evaluated on the rank the ring names and answered where its payload arrived — the decision WHERE a
  *                           payload's items go (gubernator.go:236-283), taken on the device
+ *   guber_wire_dev_eval_mesh_enc  the same, answered as serialized GetRateLimitsResp bytes with the owner's address on every answer another
+ *                           rank owns (metadata "owner"): encoded on the device, RPC by RPC
  *   guber_wire_dev_columns  the decoded columns copied to host memory (keys as rows of key_stride bytes + key_len): what
  *                           guber_wire_encode_responses-style code and the tests read */
 #define GUBER_WIRE_PRE_DEAD 255
@@ -185,6 +214,34 @@ int guber_wire_dev_eval_front(guber_wire_dev_t* d, guber_front_t* f, guber_resul
  * two ranks, a decoder whose engine is on another device than its rank's front, two non-empty decoders with different now_ms, a missing
  * result array where n_items > 0; GUBER_E_BATCH_TOO_LARGE: n_items above the mesh's max_n. */
 int guber_wire_dev_eval_mesh(guber_wire_dev_t* const* decs /* [n_ranks] */, guber_mesh_t* m, guber_result_t* results /* [n_ranks] */);
+/* The same with SERIALIZED RESPONSES: what V1Instance.GetRateLimits hands its gRPC layer in a cluster, with nothing per item on the host.  After
+ * the mesh's last hop every rank's answers are encoded on its device (k_wire_enc_owner: one workgroup per RPC, the peers' metadata suffixes
+ * copied from a table in LDS; the ring's owner per item is k_mx_count's optional output) into pinned memory of the decoder, and every RPC's
+ * GetRateLimitsResp — guber_wire_encode_responses_owner's bytes, with rank r as self_rank — is copied to out[r].buf, back to back:
+ *   out[r].off[q], out[r].len[q]   RPC q of decs[r]'s last decode (len 0: the decode turned it away, or it holds no item)
+ *   out[r].owner_rank              optional: [n_items] the ring's owner per item, 0xFF = none
+ * An RPC with an item error is re-decoded from the decoder's staging buffer by the host transcoder and written by
+ * guber_wire_encode_responses_owner (the texts need the item's key).  owner_addr[p] is the name peer p was given in guber_ring_create.
+ * out[r].cap >= guber_wire_dev_mesh_enc_bound(decs[r], owner_addr, n_ranks): the worst case INCLUDING error texts for the decoder's last
+ * decode (0: nothing to answer, or refused addresses) — the call never finds a buffer too small after decisions have been applied, and the
+ * host transcoder's batch is allocated before anything is enqueued.  (What can still fail afterwards is a HIP error, or the device's and the
+ * host's decoders disagreeing about a payload, GUBER_E_HIP: a defect, not a condition of the input.)
+ * Synchronous; refuses what guber_wire_dev_eval_mesh refuses and, as GUBER_E_INVALID_ARG, a NULL, empty or over-long address or a missing
+ * out array; a cap below the bound is GUBER_E_NOMEM.  Every refusal comes before anything is enqueued: no engine is touched. */
+typedef struct guber_wire_mesh_resp {
+    uint8_t* buf; size_t cap;          /* caller's host memory for rank r's responses */
+    uint32_t *off, *len;               /* [RPCs of decs[r]'s last decode]: RPC q's GetRateLimitsResp = buf + off[q], len[q] bytes */
+    uint8_t* owner_rank;               /* optional, [n_items]: the ring's owner per item, 0xFF = none */
+} guber_wire_mesh_resp_t;
+size_t guber_wire_dev_mesh_enc_bound(const guber_wire_dev_t* d, const char* const* owner_addr, uint32_t n_ranks);
+/* DIAGNOSTIC, not part of the serving interface (tests and measurements read them):
+ *   guber_wire_dev_mesh_enc_host_rpcs  how many RPCs of d's last guber_wire_dev_eval_mesh_enc the host transcoder wrote (they held an item
+ *                                      error); the device wrote the others
+ *   guber_wire_dev_mesh_enc_piece      the items k_wire_enc_owner encodes per piece: RPCs around it are the encoder's edge cases */
+uint32_t guber_wire_dev_mesh_enc_piece(void);
+uint32_t guber_wire_dev_mesh_enc_host_rpcs(const guber_wire_dev_t* d);
+int guber_wire_dev_eval_mesh_enc(guber_wire_dev_t* const* decs, guber_mesh_t* m, const char* const* owner_addr /* [n_ranks] */,
+                                 int wrap_errors, guber_wire_mesh_resp_t* out /* [n_ranks] */);
 int guber_wire_dev_columns(guber_wire_dev_t* d, guber_wire_columns_t* c);
 /* The same in two halves each, for a caller that keeps several decoders busy and never blocks on the GPU (the payload stage below):
  *   guber_wire_dev_set_stream           the decode's copies and kernels go to `stream` (hipStream_t) instead of the engine's stream

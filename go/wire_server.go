@@ -7,12 +7,13 @@
 //
 // NOT compiled in this repository (no Go toolchain in the build image): the calls below are made, in the same order and with the same
 // arguments, by tests/hostsim/abi_c99.c (wire_pool_sequence) and tests/hostsim/peer_abi_c99.c (the two peer handlers) — compiled as C99
-// against the public headers and run on the GPU.
+// against the public headers and run on the GPU; MeshWireServer's by tests/hostsim/mesh_pool_abi_c99.c.
 package gubernator
 
 /*
 #cgo CFLAGS: -I${SRCDIR}/../include
 #cgo LDFLAGS: -L${SRCDIR}/../gubernator_amd -lguber_hip
+#include <stdlib.h>
 #include "guber_gpu.h"
 #include "guber_wire.h"
 */
@@ -20,6 +21,7 @@ import "C"
 
 import (
 	"context"
+	"sync/atomic"
 	"unsafe"
 
 	"google.golang.org/grpc"
@@ -160,4 +162,84 @@ func (s *WireServer) ServiceDescs() (grpc.ServiceDesc, grpc.ServiceDesc) {
 		}
 	}
 	return v1, peers
+}
+
+// MeshWireServer owns the payload stage over a MESH (guber_wire_mesh_pool_*, INTEGRATION.md section 3h): one daemon in front of several GPUs,
+// every GPU a rank of a guber_mesh_t and a peer of the ring.  The handler hands the bytes of the GetRateLimitsReq to ANY rank; the ring's owner
+// decision (gubernator.go:236-283), the evaluation on the owner and the marshalling — with metadata{"owner": <address>} on every answer another
+// rank owns — happen on the devices.  GetPeerRateLimits and UpdatePeerGlobals are not served here: every peer of the ring is a local rank.
+type MeshWireServer struct {
+	pool  *C.guber_wire_mesh_pool_t
+	ranks uint32
+	next  uint32 // the rank the next RPC arrives at: round robin
+	addrs []*C.char
+}
+
+// NewMeshWireServer: the mesh (the daemon keeps it, its fronts and their engines, and destroys them after Close), the ring's peer names —
+// ownerAddr[r] is the address peer r was given in guber_ring_create — and the defaults of guber_wire_mesh_pool_config_t with the error texts
+// of gubernator.go:250-255.
+func NewMeshWireServer(mesh *C.guber_mesh_t, ownerAddr []string) (*MeshWireServer, error) {
+	s := &MeshWireServer{ranks: uint32(len(ownerAddr))}
+	for _, a := range ownerAddr {
+		s.addrs = append(s.addrs, C.CString(a))
+	}
+	var cfg C.guber_wire_mesh_pool_config_t
+	cfg.wrap_errors = 1
+	if rc := C.guber_wire_mesh_pool_create(mesh, &s.addrs[0], &cfg, &s.pool); rc != C.GUBER_OK {
+		s.free()
+		return nil, status.Errorf(codes.Internal, "guber_wire_mesh_pool_create: %s", C.GoString(C.guber_last_error()))
+	}
+	return s, nil
+}
+
+func (s *MeshWireServer) free() {
+	for _, a := range s.addrs {
+		C.free(unsafe.Pointer(a))
+	}
+	s.addrs = nil
+}
+
+// Close: no call may be in flight or arrive any more (the gRPC servers have been stopped); before the mesh is destroyed.
+func (s *MeshWireServer) Close() {
+	C.guber_wire_mesh_pool_destroy(s.pool)
+	s.free()
+}
+
+// getRateLimitsMeshRaw: the GetRateLimits handler over the mesh (the signature grpc.MethodDesc.Handler wants).  rank = a counter modulo the
+// ranks; the buffer is guber_wire_mesh_pool_response_bound's, so nothing is ever found too small after decisions have been applied.
+func (s *MeshWireServer) getRateLimitsMeshRaw(_ interface{}, _ context.Context, dec func(interface{}) error, _ grpc.UnaryServerInterceptor) (interface{}, error) {
+	in := new(rawMessage)
+	if err := dec(in); err != nil {
+		return nil, err
+	}
+	if len(in.b) == 0 {
+		return &rawMessage{}, nil // no requests: an empty GetRateLimitsResp
+	}
+	rank := C.uint32_t((atomic.AddUint32(&s.next, 1) - 1) % s.ranks)
+	p := (*C.uint8_t)(unsafe.Pointer(&in.b[0]))
+	out := make([]byte, int(C.guber_wire_mesh_pool_response_bound(s.pool, p, C.size_t(len(in.b)))))
+	var n C.size_t
+	// blocks (a cgo call: the goroutine keeps its thread) until the stage set the payload joined has been through the GPUs
+	switch rc := C.guber_wire_mesh_pool_get_rate_limits(s.pool, rank, p, C.size_t(len(in.b)), (*C.uint8_t)(unsafe.Pointer(&out[0])), C.size_t(len(out)), &n); rc {
+	case C.GUBER_OK:
+		return &rawMessage{out[:int(n)]}, nil
+	case C.GUBER_E_WIRE_TOO_LARGE: // gubernator.go:189-193
+		return nil, status.Errorf(codes.OutOfRange, "Requests.RateLimits list too large; max size is '%d'", maxBatchSize)
+	case C.GUBER_E_WIRE_MALFORMED: // what protobuf-go's Unmarshal failure becomes in grpc-go
+		return nil, status.Error(codes.Internal, "grpc: error unmarshalling request")
+	default:
+		return nil, status.Errorf(codes.Internal, "guber_wire_mesh_pool: %s", C.GoString(C.guber_last_error()))
+	}
+}
+
+// ServiceDesc: V1_ServiceDesc with GetRateLimits replaced (HealthCheck keeps its generated handler).
+func (s *MeshWireServer) ServiceDesc() grpc.ServiceDesc {
+	v1 := V1_ServiceDesc
+	v1.Methods = append([]grpc.MethodDesc(nil), v1.Methods...)
+	for i := range v1.Methods {
+		if v1.Methods[i].MethodName == "GetRateLimits" {
+			v1.Methods[i].Handler = s.getRateLimitsMeshRaw
+		}
+	}
+	return v1
 }

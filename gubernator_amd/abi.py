@@ -65,6 +65,17 @@ class GuberKernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_uint64), ("total_ms", C.c_double), ("units", C.c_uint64)]
 
 
+class WireMeshPoolConfig(C.Structure):
+    """guber_wire_mesh_pool_config_t (include/guber_wire.h); a zero field = its default"""
+    _fields_ = [(k, C.c_uint32) for k in ("sets", "max_items", "max_payload_bytes", "max_rpcs", "batch_wait_us", "max_per_rpc", "wrap_errors")]
+
+
+class WireMeshPoolStats(C.Structure):
+    """guber_wire_mesh_pool_stats_t"""
+    _fields_ = [(k, C.c_uint64) for k in ("rpcs", "items", "sets", "sealed_full", "sealed_wait", "sealed_idle", "forwarded", "host_rpcs", "open_waits",
+                                           "fill_us_sum", "gpu_us_sum")]
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data
 

@@ -250,3 +250,4 @@ extern "C" const char* guber_last_error(void) { return g_last_error.c_str(); }
 #include "guber_wire_dev.h"     // (behind the mesh: guber_wire_dev_eval_mesh feeds it)
 #include "guber_wire_pool.h"    // guber_wire_pool_*: the payload stage (caller threads hand over serialized RPCs)
 #include "guber_wire_pool_peer.h"   // guber_wire_pool_update_peer_globals: a broadcast of GLOBAL buckets installed through the pool's rule
+#include "guber_wire_mesh_pool.h"   // guber_wire_mesh_pool_*: the payload stage over a mesh (RPC bytes in at any rank, response bytes out)

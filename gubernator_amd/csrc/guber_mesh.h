@@ -311,7 +311,9 @@ static int mesh_eval(guber_mesh* m, const guber_batch_t* gens, const guber_mesh_
 // rows[r].key_stride != 0: rank r's keys lie in ROWS (gens[r].key_bytes the first row, key_stride bytes apart, key_len[i] bytes of row i
 // are the key; gens[r].key_off NULL) — what the device wire decoder leaves; rows NULL or key_stride 0: packed.  Every check comes
 // before the first HIP call.
-static int mesh_eval_rows_owner(guber_mesh_t* m, const guber_batch_t* gens, const guber_mesh_rows_t* rows, guber_result_t* results, uint8_t* const* item_owner) {
+// forwarded: NULL, or the requests THIS call moved to another rank (the counter's step, taken under the mesh's lock)
+static int mesh_eval_rows_owner(guber_mesh_t* m, const guber_batch_t* gens, const guber_mesh_rows_t* rows, guber_result_t* results, uint8_t* const* item_owner,
+                                uint64_t* forwarded = nullptr) {
     if (!m || !gens || !results) return fail(GUBER_E_INVALID_ARG, "null argument");
     for (uint32_t r = 0; r < m->W; ++r) {
         int rc;
@@ -332,7 +334,9 @@ static int mesh_eval_rows_owner(guber_mesh_t* m, const guber_batch_t* gens, cons
     }
     std::lock_guard<std::mutex> lk(m->mu);
     const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t fwd0 = m->st.forwarded;
     const int rc = mesh_eval(m, gens, rows, results, item_owner);
+    if (forwarded) *forwarded = m->st.forwarded - fwd0;
     m->st.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return rc;
 }

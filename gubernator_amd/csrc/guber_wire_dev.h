@@ -435,14 +435,13 @@ extern "C" size_t guber_wire_dev_mesh_enc_bound(const guber_wire_dev_t* d, const
 }
 extern "C" uint32_t guber_wire_dev_mesh_enc_piece(void) { return guber::WEO_P; }
 extern "C" uint32_t guber_wire_dev_mesh_enc_host_rpcs(const guber_wire_dev_t* d) { return d ? d->menc.host_rpcs : 0u; }
-// one RPC the device left raw: its payload once more through the host transcoder, the raw answers filled in, guber_wire_encode_responses_owner
-// (wb: made before anything was enqueued, large enough for the decode's largest RPC)
-static int wire_mesh_enc_host_rpc(guber_wire_dev* d, guber_wire_batch_t* wb, uint32_t q, uint32_t first, uint32_t count, const guber_result_t& raw, const uint8_t* owner, uint32_t self,
-                                  const char* const* owner_addr, uint32_t n_ranks, int wrap_errors, uint8_t* out, size_t cap, size_t* used) {
-    const uint32_t* h_off = d->h_meta(); const uint32_t* h_len = h_off + d->max_rpcs;
-    guber_wire_batch_reset(wb, d->now_ms);
+// one RPC the device left raw: its payload (req, len: the bytes as they arrived) once more through the host transcoder at the decode's now_ms,
+// the raw answers filled in, guber_wire_encode_responses_owner (wb: made before anything was enqueued, large enough for the RPC)
+static int wire_mesh_enc_host_rpc(guber_wire_batch_t* wb, const uint8_t* req, size_t len, int64_t now_ms, uint32_t first, uint32_t count, const guber_result_t& raw,
+                                  const uint8_t* owner, uint32_t self, const char* const* owner_addr, uint32_t n_ranks, int wrap_errors, uint8_t* out, size_t cap, size_t* used) {
+    guber_wire_batch_reset(wb, now_ms);
     uint32_t f0 = 0, c0 = 0;
-    int rc = guber_wire_decode_requests(wb, d->h_pay() + h_off[q], h_len[q], 0, 1, &f0, &c0);
+    int rc = guber_wire_decode_requests(wb, req, len, 0, 1, &f0, &c0);
     if (!rc && c0 != count) rc = GUBER_E_HIP;
     if (rc) return fail(GUBER_E_HIP, "guber_wire_dev_eval_mesh_enc: the device's and the host's decoders disagree about a payload");
     guber_result_t* hr = guber_wire_batch_result(wb);
@@ -453,23 +452,113 @@ static int wire_mesh_enc_host_rpc(guber_wire_dev* d, guber_wire_batch_t* wb, uin
     if (rc) return fail(rc, "guber_wire_dev_eval_mesh_enc: an RPC's responses did not fit the bound");
     return GUBER_OK;
 }
+// guber_wire_dev_eval_mesh_enc in two parts.  The first (wire_mesh_enc_device) runs to "the device is done": per rank, where k_wire_enc_owner
+// left every RPC's bytes (enc at wire_enco_off(first, q, item_max), enc_len[q] of them, or WIRE_ENC_RAW and the raw answers), and the ring's
+// owner per item in host memory.  The second copies out: the public function's tail below, or — RPC by RPC, each by its own caller — the
+// payload stage over a mesh (guber_wire_mesh_pool.h).
+// the peers' suffixes: they depend on the addresses alone, so one table serves every call over the same ring
+struct WireMeshSfx { std::vector<uint8_t> sfx; std::vector<uint32_t> len; uint32_t item_max = 0; size_t longest = 0; };
+static int wire_mesh_sfx_build(const char* const* owner_addr, uint32_t W, WireMeshSfx& T) {
+    T.longest = guber::wire::owner_suffix_longest(owner_addr, W, guber::WEO_RANKS);
+    if (!T.longest) return GUBER_E_INVALID_ARG;
+    T.item_max = 1u + 2u + guber::wire::RESP_BODY_MAX + (uint32_t)T.longest;          // no item of a call takes more
+    T.sfx.assign((size_t)guber::WEO_RANKS * guber::WEO_SFX_STRIDE, 0); T.len.assign(guber::WEO_RANKS, 0);
+    for (uint32_t p = 0; p < W; ++p) T.len[p] = guber::wire::put_owner_suffix(T.sfx.data() + (size_t)p * guber::WEO_SFX_STRIDE, owner_addr[p], (uint32_t)strlen(owner_addr[p]));
+    return GUBER_OK;
+}
+struct WireMeshEncDone { const uint8_t* enc = nullptr; const uint32_t* enc_len = nullptr; guber_result_t raw{}; const uint8_t* h_owner = nullptr; uint32_t item_max = 0; };
+// a decoder's buffers for `items` items in `rpcs` RPCs (engine mutex held, device set; nothing is enqueued) -> where the raw answers go
+static int wire_mesh_enc_ensure(guber_wire_dev* d, uint32_t items, uint32_t rpcs, const WireMeshSfx& T, guber_result_t* raw) {
+    WireMeshEnc* x = &d->menc;
+    const size_t M = d->max_items, col8 = (M + 63) & ~(size_t)63;
+    if (x->d_owner.ensure(M) || x->d_sfx.ensure(T.sfx.size()) || x->d_sfx_len.ensure(guber::WEO_RANKS) || x->h_sfx.ensure(T.sfx.size() + 4 * guber::WEO_RANKS) ||
+        x->h_owner.ensure(M) || x->enc.ensure(guber::wire_enco_bytes(items, rpcs, T.item_max)) || x->res.ensure(2 * col8 + 3 * 8 * M + 64) ||
+        x->enc_len.ensure(d->max_rpcs)) return GUBER_E_NOMEM;
+    uint8_t* q = x->res.p;
+    *raw = guber_result_t{};
+    raw->status = q; q += col8; raw->err = q; q += col8;
+    raw->limit = (int64_t*)q; q += 8 * M; raw->remaining = (int64_t*)q; q += 8 * M; raw->reset_time = (int64_t*)q;
+    return GUBER_OK;
+}
+// the table to the decoder's HBM, enqueued on st (engine mutex held, device set)
+static int wire_mesh_enc_put_sfx(guber_wire_dev* d, const WireMeshSfx& T, hipStream_t st) {
+    WireMeshEnc* x = &d->menc;
+    memcpy(x->h_sfx.p, T.sfx.data(), T.sfx.size()); memcpy(x->h_sfx.p + T.sfx.size(), T.len.data(), 4 * guber::WEO_RANKS);
+    HIPCHK(hipMemcpyAsync(x->d_sfx.p, x->h_sfx.p, T.sfx.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(x->d_sfx_len.p, x->h_sfx.p + T.sfx.size(), 4 * guber::WEO_RANKS, hipMemcpyHostToDevice, st));
+    return GUBER_OK;
+}
+// decs as wire_dev_mesh_check left them (now_ms: its answer).  sfx_resident: every decoder holds T already (the payload stage uploads it once,
+// when it is created) — otherwise the table travels with the call.  done[r] is filled for every rank with items; returns when every rank's
+// encoder and owner column have arrived in host memory — or, wait = false, when they are enqueued: the caller waits rank by rank
+// (wire_mesh_enc_wait) and copies one rank out while the next ones' encoders still run.
+static int wire_mesh_enc_wait(guber_wire_dev* d) {
+    std::lock_guard<std::mutex> lk(d->e->mu);
+    if (d->e->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
+    HIPCHK(hipStreamSynchronize(d->stream()));
+    return GUBER_OK;
+}
+static int wire_mesh_enc_device(guber_wire_dev_t* const* decs, guber_mesh_t* m, int64_t now_ms, const WireMeshSfx& T, bool sfx_resident, bool wait, WireMeshEncDone* done,
+                                uint64_t* forwarded = nullptr) {
+    const uint32_t W = m->W;
+    std::vector<guber_result_t> raw(W, guber_result_t{});
+    for (uint32_t r = 0; r < W; ++r) {                                                      // (allocations: nothing is enqueued yet)
+        guber_wire_dev* d = decs[r];
+        done[r] = WireMeshEncDone{};
+        if (!d || !d->n_items) continue;
+        std::lock_guard<std::mutex> lk(d->e->mu);
+        if (d->e->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
+        { const int rc = wire_mesh_enc_ensure(d, d->n_items, d->nrpc, T, &raw[r]); if (rc) return rc; }
+    }
+    std::vector<guber_batch_t> gens; std::vector<guber_mesh_rows_t> rows; std::vector<guber_result_t> dr;
+    wire_dev_mesh_gens(decs, W, now_ms, gens, rows, dr);
+    std::vector<uint8_t*> item_owner(W, nullptr);
+    for (uint32_t r = 0; r < W; ++r) if (decs[r] && decs[r]->n_items) item_owner[r] = decs[r]->menc.d_owner.p;
+    { const int rc = mesh_eval_rows_owner(m, gens.data(), rows.data(), dr.data(), item_owner.data(), forwarded); if (rc) return rc; }
+    { const int rc = guber_mesh_synchronize(m); if (rc) return rc; }
+    // the encoder, once per rank, behind the mesh's last hop
+    for (uint32_t r = 0; r < W; ++r) {
+        guber_wire_dev* d = decs[r];
+        if (!d || !d->n_items) continue;
+        WireMeshEnc* x = &d->menc;
+        guber_engine* e = d->e;
+        std::lock_guard<std::mutex> lk(e->mu);
+        if (e->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
+        hipStream_t st = d->stream();
+        if (!sfx_resident) { const int rc = wire_mesh_enc_put_sfx(d, T, st); if (rc) return rc; }
+        guber::WireEncOwner A{};
+        guber::WireEnc& E = A.E;
+        E.nrpc = d->nrpc; E.first = d->sc.first; E.count = d->sc.count; E.status = d->sc.status;
+        E.d_status = dr[r].status; E.d_err = dr[r].err; E.d_limit = dr[r].limit; E.d_remaining = dr[r].remaining; E.d_reset = dr[r].reset_time;
+        E.enc = x->enc.p; E.enc_len = x->enc_len.p;
+        E.h_status = raw[r].status; E.h_err = raw[r].err; E.h_limit = raw[r].limit; E.h_remaining = raw[r].remaining; E.h_reset = raw[r].reset_time;
+        A.item_owner = x->d_owner.p; A.self = r; A.n_ranks = W; A.item_max = T.item_max; A.sfx = x->d_sfx.p; A.sfx_len = x->d_sfx_len.p;
+        hipLaunchKernelGGL(guber::k_wire_enc_owner, dim3(d->nrpc), dim3(guber::WEO_T), 0, st, A);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(x->h_owner.p, x->d_owner.p, d->n_items, hipMemcpyDeviceToHost, st));
+        done[r].enc = x->enc.p; done[r].enc_len = x->enc_len.p; done[r].raw = raw[r]; done[r].h_owner = x->h_owner.p; done[r].item_max = T.item_max;
+    }
+    for (uint32_t r = 0; r < W && wait; ++r) {
+        guber_wire_dev* d = decs[r];
+        if (!d || !d->n_items) continue;
+        const int rc = wire_mesh_enc_wait(d);
+        if (rc) return rc;
+    }
+    return GUBER_OK;
+}
 extern "C" int guber_wire_dev_eval_mesh_enc(guber_wire_dev_t* const* decs, guber_mesh_t* m, const char* const* owner_addr, int wrap_errors, guber_wire_mesh_resp_t* out) {
     if (!decs || !m || !owner_addr || !out) return fail(GUBER_E_INVALID_ARG, "null argument");
     const uint32_t W = m->W;
     int64_t now_ms = 0;
     { const int rc = wire_dev_mesh_check(decs, m, &now_ms); if (rc) return rc; }
-    const size_t longest = guber::wire::owner_suffix_longest(owner_addr, W, guber::WEO_RANKS);
-    if (!longest) return fail(GUBER_E_INVALID_ARG, "guber_wire_dev_eval_mesh_enc: every rank has an address of 1 .. GUBER_WIRE_OWNER_ADDR_MAX bytes");
+    WireMeshSfx T;                                                                          // the peers' suffixes, once per call
+    if (wire_mesh_sfx_build(owner_addr, W, T)) return fail(GUBER_E_INVALID_ARG, "guber_wire_dev_eval_mesh_enc: every rank has an address of 1 .. GUBER_WIRE_OWNER_ADDR_MAX bytes");
     for (uint32_t r = 0; r < W; ++r) {
         guber_wire_dev* d = decs[r];
         if (!d || !d->nrpc) continue;
         if (!out[r].off || !out[r].len || (d->n_items && (!out[r].buf))) return fail(GUBER_E_INVALID_ARG, "guber_wire_dev_eval_mesh_enc: a rank's response arrays are missing");
         if (out[r].cap < guber_wire_dev_mesh_enc_bound(d, owner_addr, W)) return fail(GUBER_E_NOMEM, "response buffer below guber_wire_dev_mesh_enc_bound()");
     }
-    // the peers' suffixes, once per call; no item of the call takes more than item_max bytes
-    const uint32_t item_max = 1u + 2u + guber::wire::RESP_BODY_MAX + (uint32_t)longest;
-    std::vector<uint8_t> sfx((size_t)guber::WEO_RANKS * guber::WEO_SFX_STRIDE, 0); std::vector<uint32_t> sfx_len(guber::WEO_RANKS, 0);
-    for (uint32_t p = 0; p < W; ++p) sfx_len[p] = guber::wire::put_owner_suffix(sfx.data() + (size_t)p * guber::WEO_SFX_STRIDE, owner_addr[p], (uint32_t)strlen(owner_addr[p]));
     for (uint32_t r = 0; r < W; ++r) if (decs[r]) decs[r]->menc.host_rpcs = 0;
     // the host transcoder's batch for the RPCs the device leaves raw: one, for the largest RPC of the call, before anything is enqueued
     struct HostBatch { guber_wire_batch_t* p = nullptr; ~HostBatch() { guber_wire_batch_destroy(p); } } hb;
@@ -486,82 +575,59 @@ extern "C" int guber_wire_dev_eval_mesh_enc(guber_wire_dev_t* const* decs, guber
         }
         if (guber_wire_batch_create(most, (uint32_t)std::min<size_t>(longest_rpc + most + 16, 0xffffffffu), 0, &hb.p)) return fail(GUBER_E_NOMEM, "guber_wire_dev_eval_mesh_enc: no memory for the host transcoder's batch");
     }
-    std::vector<WireMeshEnc*> X(W, nullptr); std::vector<guber_result_t> raw(W, guber_result_t{});
-    for (uint32_t r = 0; r < W; ++r) {                                                      // (allocations: nothing is enqueued yet)
-        guber_wire_dev* d = decs[r];
-        if (!d || !d->n_items) continue;
-        std::lock_guard<std::mutex> lk(d->e->mu);
-        if (d->e->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
-        WireMeshEnc* x = X[r] = &d->menc;
-        const size_t M = d->max_items, col8 = (M + 63) & ~(size_t)63;
-        if (x->d_owner.ensure(M) || x->d_sfx.ensure(sfx.size()) || x->d_sfx_len.ensure(guber::WEO_RANKS) || x->h_sfx.ensure(sfx.size() + 4 * guber::WEO_RANKS) ||
-            x->h_owner.ensure(M) || x->enc.ensure(guber::wire_enco_bytes(d->n_items, d->nrpc, item_max)) || x->res.ensure(2 * col8 + 3 * 8 * M + 64) ||
-            x->enc_len.ensure(d->max_rpcs)) return GUBER_E_NOMEM;
-        uint8_t* q = x->res.p;
-        raw[r].status = q; q += col8; raw[r].err = q; q += col8;
-        raw[r].limit = (int64_t*)q; q += 8 * M; raw[r].remaining = (int64_t*)q; q += 8 * M; raw[r].reset_time = (int64_t*)q;
-    }
-    std::vector<guber_batch_t> gens; std::vector<guber_mesh_rows_t> rows; std::vector<guber_result_t> dr;
-    wire_dev_mesh_gens(decs, W, now_ms, gens, rows, dr);
-    std::vector<uint8_t*> item_owner(W, nullptr);
-    for (uint32_t r = 0; r < W; ++r) if (X[r]) item_owner[r] = X[r]->d_owner.p;
-    { const int rc = mesh_eval_rows_owner(m, gens.data(), rows.data(), dr.data(), item_owner.data()); if (rc) return rc; }
-    { const int rc = guber_mesh_synchronize(m); if (rc) return rc; }
-    // the encoder, once per rank, behind the mesh's last hop; then the bytes, RPC by RPC
-    for (uint32_t r = 0; r < W; ++r) {
-        guber_wire_dev* d = decs[r];
-        if (!d || !d->n_items) continue;
-        WireMeshEnc* x = X[r];
-        guber_engine* e = d->e;
-        std::lock_guard<std::mutex> lk(e->mu);
-        if (e->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
-        hipStream_t st = d->stream();
-        memcpy(x->h_sfx.p, sfx.data(), sfx.size()); memcpy(x->h_sfx.p + sfx.size(), sfx_len.data(), 4 * guber::WEO_RANKS);
-        HIPCHK(hipMemcpyAsync(x->d_sfx.p, x->h_sfx.p, sfx.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(x->d_sfx_len.p, x->h_sfx.p + sfx.size(), 4 * guber::WEO_RANKS, hipMemcpyHostToDevice, st));
-        guber::WireEncOwner A{};
-        guber::WireEnc& E = A.E;
-        E.nrpc = d->nrpc; E.first = d->sc.first; E.count = d->sc.count; E.status = d->sc.status;
-        E.d_status = dr[r].status; E.d_err = dr[r].err; E.d_limit = dr[r].limit; E.d_remaining = dr[r].remaining; E.d_reset = dr[r].reset_time;
-        E.enc = x->enc.p; E.enc_len = x->enc_len.p;
-        E.h_status = raw[r].status; E.h_err = raw[r].err; E.h_limit = raw[r].limit; E.h_remaining = raw[r].remaining; E.h_reset = raw[r].reset_time;
-        A.item_owner = x->d_owner.p; A.self = r; A.n_ranks = W; A.item_max = item_max; A.sfx = x->d_sfx.p; A.sfx_len = x->d_sfx_len.p;
-        hipLaunchKernelGGL(guber::k_wire_enc_owner, dim3(d->nrpc), dim3(guber::WEO_T), 0, st, A);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(x->h_owner.p, x->d_owner.p, d->n_items, hipMemcpyDeviceToHost, st));
-    }
+    std::vector<WireMeshEncDone> done(W);
+    { const int rc = wire_mesh_enc_device(decs, m, now_ms, T, false, false, done.data()); if (rc) return rc; }
+    // the bytes, RPC by RPC
     for (uint32_t r = 0; r < W; ++r) {
         guber_wire_dev* d = decs[r];
         if (!d || !d->nrpc) continue;
         guber_wire_mesh_resp_t& o = out[r];
         if (!d->n_items) { for (uint32_t q = 0; q < d->nrpc; ++q) { o.off[q] = 0; o.len[q] = 0; } continue; }
-        WireMeshEnc* x = X[r];
-        {
-            std::lock_guard<std::mutex> lk(d->e->mu);
-            if (d->e->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
-            HIPCHK(hipStreamSynchronize(d->stream()));
-        }
+        { const int rc = wire_mesh_enc_wait(d); if (rc) return rc; }
+        const WireMeshEncDone& x = done[r];
+        const uint32_t* h_off = d->h_meta(); const uint32_t* h_len = h_off + d->max_rpcs;
         const volatile uint32_t* h_first = d->out.rep_first; const volatile uint32_t* h_count = d->out.rep_count; const volatile int32_t* h_status = d->out.rep_status;
-        if (o.owner_rank) memcpy(o.owner_rank, x->h_owner.p, d->n_items);
+        if (o.owner_rank) memcpy(o.owner_rank, x.h_owner, d->n_items);
         size_t at = 0;
         for (uint32_t q = 0; q < d->nrpc; ++q) {
             const uint32_t first = h_first[q], count = h_status[q] == GUBER_OK ? h_count[q] : 0u;
             o.off[q] = (uint32_t)at; o.len[q] = 0;
             if (!count) continue;
-            const uint32_t el = x->enc_len.p[q];
+            const uint32_t el = x.enc_len[q];
             size_t used = 0;
             if (el != guber::WIRE_ENC_RAW) {
                 if (el > o.cap - at) return fail(GUBER_E_HIP, "guber_wire_dev_eval_mesh_enc: the device's responses exceed the bound");
-                memcpy(o.buf + at, x->enc.p + guber::wire_enco_off(first, q, item_max), el); used = el;
+                memcpy(o.buf + at, x.enc + guber::wire_enco_off(first, q, x.item_max), el); used = el;
             } else {
-                const int rc = wire_mesh_enc_host_rpc(d, hb.p, q, first, count, raw[r], x->h_owner.p, r, owner_addr, W, wrap_errors, o.buf + at, o.cap - at, &used);
+                const int rc = wire_mesh_enc_host_rpc(hb.p, d->h_pay() + h_off[q], h_len[q], d->now_ms, first, count, x.raw, x.h_owner, r, owner_addr, W, wrap_errors, o.buf + at, o.cap - at, &used);
                 if (rc) return rc;
-                x->host_rpcs++;
+                d->menc.host_rpcs++;
             }
             o.len[q] = (uint32_t)used; at += used;
         }
     }
     return GUBER_OK;
+}
+// ---- what the payload stage over a mesh (guber_wire_mesh_pool.h) asks of this file: the mesh's shape, a rank's decoder engine, the table in a
+// decoder's HBM once and for all (buffers for the decoder's largest decode: no call of the pool allocates), and one set's way from its
+// collected decodes to "the device is done" (*forwarded: the items it moved to another rank)
+static void wire_mesh_pool_shape(guber_mesh_t* m, uint32_t* W, uint32_t* max_n) { *W = m->W; *max_n = m->max_n; }
+static guber_engine_t* wire_mesh_pool_engine(guber_mesh_t* m, uint32_t r, uint32_t* max_batch) { guber_engine* e = m->ranks[r].f->eng[0]; *max_batch = e->max_batch; return e; }
+static int wire_mesh_pool_prepare(guber_wire_dev* d, const WireMeshSfx& T) {
+    guber_engine* e = d->e;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->set_device()) return fail(GUBER_E_HIP, "hipSetDevice");
+    guber_result_t raw;
+    { const int rc = wire_mesh_enc_ensure(d, d->max_items, d->max_rpcs, T, &raw); if (rc) return rc; }
+    { const int rc = wire_mesh_enc_put_sfx(d, T, d->stream()); if (rc) return rc; }
+    HIPCHK(hipStreamSynchronize(d->stream()));
+    return GUBER_OK;
+}
+static int wire_mesh_pool_eval(guber_wire_dev_t* const* decs, guber_mesh_t* m, const WireMeshSfx& T, WireMeshEncDone* done, uint64_t* forwarded) {
+    int64_t now_ms = 0;
+    *forwarded = 0;
+    { const int rc = wire_dev_mesh_check(decs, m, &now_ms); if (rc) return rc; }
+    return wire_mesh_enc_device(decs, m, now_ms, T, true, true, done, forwarded);
 }
 // guber_wire_dev_eval_front_async   the same, enqueued only: `r`'s arrays are DEVICE-VISIBLE (HBM, or host memory the device writes in
 //                                   place over PCIe: hipHostMalloc / guber_alloc_pinned) — the answers' last hop (k_fr_out) writes them where

@@ -8,7 +8,7 @@ import numpy as np
 from . import GuberError, lib
 from .abi import GuberBatch, GuberResult
 
-E_WIRE_MALFORMED, E_WIRE_TOO_LARGE, E_WIRE_FULL = -20, -21, -22
+E_WIRE_MALFORMED, E_WIRE_TOO_LARGE, E_WIRE_FULL, E_WIRE_CLOSED = -20, -21, -22, -23
 RPC_OWNER, RPC_PEER = 1, 2            # GUBER_WIRE_RPC_*: the per-RPC flag byte of the device decoder and the payload stage
 WIRE_SYMBOLS = [
     "guber_wire_batch_create", "guber_wire_batch_destroy", "guber_wire_batch_reset", "guber_wire_batch_size",
@@ -23,6 +23,8 @@ WIRE_SYMBOLS = [
     "guber_wire_pool_create", "guber_wire_pool_destroy", "guber_wire_pool_get_rate_limits", "guber_wire_pool_response_bound",
     "guber_wire_pool_get_peer_rate_limits", "guber_wire_pool_update_peer_globals",
     "guber_wire_pool_set_clock", "guber_wire_pool_stats",
+    "guber_wire_mesh_pool_create", "guber_wire_mesh_pool_destroy", "guber_wire_mesh_pool_get_rate_limits", "guber_wire_mesh_pool_response_bound",
+    "guber_wire_mesh_pool_set_clock", "guber_wire_mesh_pool_stats",
 ]
 _bound = False
 
@@ -480,6 +482,77 @@ class WirePool:
     def close(self):
         if getattr(self, "h", None):
             self.L.guber_wire_pool_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class WireMeshPool:
+    """guber_wire_mesh_pool_* (include/guber_wire.h): the payload stage over a mesh — serialized GetRateLimitsReq bytes in at any rank,
+    serialized GetRateLimitsResp bytes out, with metadata{"owner": owner_addr[p]} on every answer that rank p, not the arrival rank, owns.
+    get_rate_limits() is what one gRPC handler thread calls; it may be called from many threads at once (the call releases the GIL).
+    The pool owns neither the mesh nor its fronts nor their engines: close it before them.  cfg: the fields of WireMeshPoolConfig."""
+
+    def __init__(self, mesh, owner_addr, **cfg):
+        from .abi import WireMeshPoolConfig, WireMeshPoolStats
+        L = self.L = _lib()
+        L.guber_wire_mesh_pool_create.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(WireMeshPoolConfig), C.POINTER(C.c_void_p)]
+        L.guber_wire_mesh_pool_destroy.argtypes = [C.c_void_p]
+        L.guber_wire_mesh_pool_destroy.restype = None
+        L.guber_wire_mesh_pool_get_rate_limits.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.guber_wire_mesh_pool_response_bound.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+        L.guber_wire_mesh_pool_response_bound.restype = C.c_size_t
+        L.guber_wire_mesh_pool_set_clock.argtypes = [C.c_void_p, C.c_int64]
+        L.guber_wire_mesh_pool_stats.argtypes = [C.c_void_p, C.POINTER(WireMeshPoolStats)]
+        self._stats = WireMeshPoolStats
+        self.mesh = mesh
+        self.addrs, arr = _addr_array(owner_addr)
+        if len(self.addrs) != len(mesh.fronts):
+            raise GuberError(-1, "guber_wire_mesh_pool: one address per rank of the mesh")
+        c = WireMeshPoolConfig(**cfg)
+        self.h = C.c_void_p()
+        rc = L.guber_wire_mesh_pool_create(mesh.h, arr, C.byref(c), C.byref(self.h))
+        if rc:
+            self.h = None
+            raise GuberError(rc, lib().guber_last_error().decode())
+
+    def _open(self):
+        if not getattr(self, "h", None):
+            raise GuberError(E_WIRE_CLOSED, "guber_wire_mesh_pool: closed")
+        return self.h
+
+    def response_bound(self, payload):
+        return self.L.guber_wire_mesh_pool_response_bound(self._open(), payload, len(payload))
+
+    def set_clock(self, now_ms):
+        self.L.guber_wire_mesh_pool_set_clock(self._open(), now_ms)
+
+    def get_rate_limits(self, rank, payload, cap=None):
+        """the serialized GetRateLimitsReq that arrived at `rank` -> serialized GetRateLimitsResp (GuberError for a message that is turned away
+        whole, with .needed = the bound when cap was below it)"""
+        h = self._open()
+        cap = self.L.guber_wire_mesh_pool_response_bound(h, payload, len(payload)) if cap is None else cap
+        buf = C.create_string_buffer(max(cap, 1))
+        n = C.c_size_t(0)
+        rc = self.L.guber_wire_mesh_pool_get_rate_limits(h, rank, payload, len(payload), buf, cap, C.byref(n))
+        if rc:
+            e = GuberError(rc, lib().guber_last_error().decode())
+            e.needed = n.value
+            raise e
+        return buf.raw[:n.value]
+
+    def stats(self):
+        st = self._stats()
+        self.L.guber_wire_mesh_pool_stats(self._open(), C.byref(st))
+        return {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.guber_wire_mesh_pool_destroy(self.h)
             self.h = None
 
     def __del__(self):

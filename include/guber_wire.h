@@ -300,8 +300,8 @@ int guber_wire_dev_route_ready(guber_wire_dev_t* d, guber_front_t* f);
  *                                     in ms, as the reference's tests use clock.Freeze
  *   What this surface does NOT do: the Store's write-through callbacks (store.go:49-65: guber_pool_set_store / guber_eval_batch_store — a daemon
  *   with conf.Store keeps the per-request pool) (the front below it has it: guber_front_eval_store_dev), metadata propagation (RateLimitReq.metadata is skipped), and the decision WHERE a payload goes
- *   (forwarding to the owning peer, gubernator.go:236-283: the threaded pool still evaluates only what its instance owns, the Go front end hands
- *   over just that; the synchronous building block that takes the decision on the device is guber_wire_dev_eval_mesh above).  Behavior_GLOBAL items
+ *   (forwarding to the owning peer, gubernator.go:236-283: this pool evaluates only what its instance owns, the Go front end hands
+ *   over just that; the payload stage that takes the decision on the devices is guber_wire_mesh_pool_* below).  Behavior_GLOBAL items
  *   are evaluated on their table and queued for the GLOBAL exchange by the engine as on every other entry point (guber_global_take / _sync);
  *   a rule whose global_engine is set sends them to the device's GLOBAL engine. */
 typedef struct guber_wire_pool guber_wire_pool_t;
@@ -333,6 +333,69 @@ int guber_wire_pool_update_peer_globals(guber_wire_pool_t* p, const uint8_t* msg
 size_t guber_wire_pool_response_bound(const uint8_t* req, size_t len);
 int guber_wire_pool_set_clock(guber_wire_pool_t* p, int64_t now_ms);
 int guber_wire_pool_stats(guber_wire_pool_t* p, guber_wire_pool_stats_t* out);
+
+/* ---- the payload stage over a MESH: RPC bytes in at any rank, response bytes out.  guber_wire_pool above serves the engines of one device;
+ *      this one lies over a guber_mesh_t (include/guber_gpu.h: one front per rank, the ring's peers), so that on a node with several GPUs the
+ *      handler threads hand the bytes of their GetRateLimitsReq to ANY rank and get GetRateLimitsResp bytes back, with metadata{"owner": <address>}
+ *      on every answer another rank owns — exactly guber_wire_dev_eval_mesh_enc's bytes with self_rank = the rank the RPC arrived at.  Decode, the
+ *      ring's owner decision (gubernator.go:236-283), the evaluation on the owner, the answers' order and the marshalling stay on the devices
+ *      (k_wire_* -> k_mx_count / k_mx_scan / k_mx_pack -> the owners' fronts -> k_mx_apack / k_mx_out -> k_wire_enc_owner).
+ *   guber_wire_mesh_pool_create            over a mesh the caller keeps (the pool owns neither the mesh nor its fronts nor their engines, and is
+ *                                          destroyed before them); owner_addr[r]: the name peer r has in the ring.  sets x n_ranks decoders, each
+ *                                          bound to the first engine of its rank's front; the owners' suffix table is uploaded once.  One
+ *                                          dispatcher thread; it may block on the GPU.  GUBER_E_INVALID_ARG: a NULL argument, a NULL, empty or
+ *                                          over-long address, a field outside its range, max_items above the mesh's max_n or above the
+ *                                          max_batch of a rank's decoder engine.
+ *   guber_wire_mesh_pool_get_rate_limits   rank: where the RPC arrived (the handler picks it, round robin for instance); req/len: one serialized
+ *                                          GetRateLimitsReq.  Blocks until the stage set the payload joined has been through the GPUs.  A stage
+ *                                          set is one stage per rank; it leaves when a rank's stage cannot take the RPC that asks, batch_wait_us
+ *                                          after its first payload, or at once while no set is on the GPUs.  The clock is read once per set, when
+ *                                          it is sealed.  Within a rank's stage items keep the order the places were taken; between ranks the
+ *                                          mesh's rule holds (owner o takes source 0, 1, ... W-1); sets are evaluated in the order they were
+ *                                          sealed: a call that has returned was evaluated before any call that starts later.
+ *                                          cap >= guber_wire_mesh_pool_response_bound(p, req, len), or GUBER_E_NOMEM (*resp_len = the bound) BEFORE
+ *                                          the RPC joins a set: nothing is ever found too small after decisions have been applied.  Turned away
+ *                                          whole, the set's other RPCs unaffected: GUBER_E_WIRE_MALFORMED; GUBER_E_WIRE_TOO_LARGE (more than
+ *                                          min(max_items, 4096, max_per_rpc) items); GUBER_E_WIRE_FULL (a payload no empty stage can hold, at the
+ *                                          door).  len == 0: an empty response, no set.  GUBER_E_INVALID_ARG: a NULL argument, rank >= n_ranks.
+ *                                          GUBER_E_WIRE_CLOSED: destroy has begun, or a set failed on the devices — that set's callers get the
+ *                                          HIP error, and the pool closes.  An RPC with an item error is marshalled by its CALLER from its own req
+ *                                          bytes through the host transcoder (the texts need the keys); the dispatcher does nothing per item.
+ *   guber_wire_mesh_pool_response_bound    items (walked, or the cap for long payloads) x (an answer with an error text + the longest owner
+ *                                          suffix) + len: everything guber_wire_dev_mesh_enc_bound counts, for one RPC
+ *   guber_wire_mesh_pool_set_clock         0 = the wall clock; otherwise a frozen clock in ms, as clock.Freeze
+ *   Other threads may keep calling guber_mesh_eval*, guber_add_items and guber_global_sync on the same objects: the mesh's and the engines' locks
+ *   serialise them, as beside guber_wire_pool.
+ *   What this surface does NOT do: GetPeerRateLimits / UpdatePeerGlobals (every peer of the mesh's ring is a local rank, nobody outside sends
+ *   them; guber_wire_pool serves them per device), the Store callbacks, a caller-evaluated fast path for a lone small RPC (guber_wire_pool's
+ *   has no counterpart here yet), non-blocking dispatch (the dispatcher waits for the GPUs phase by phase), an RCCL transport and one rank per
+ *   process (guber_mesh_create_local's ranks live in this process). */
+typedef struct guber_wire_mesh_pool guber_wire_mesh_pool_t;
+typedef struct guber_wire_mesh_pool_config {
+    uint32_t sets;               /* stage sets in rotation (one fills while another is on the GPUs); 0 = 3, 2 .. 8 */
+    uint32_t max_items;          /* items one rank's stage holds; 0 = min(49 152, the mesh's max_n, the rank's decoder engine's max_batch) */
+    uint32_t max_payload_bytes;  /* per rank and stage; 0 = 8 MiB (<= 16 MiB) */
+    uint32_t max_rpcs;           /* per rank and stage; 0 = 1024 (<= 4095) */
+    uint32_t batch_wait_us;      /* a set leaves at the latest this long after its first payload; 0 = 500 (BatchWait, config.go:131) */
+    uint32_t max_per_rpc;        /* 0 = 1000 (gubernator.go:40); 0xffffffff = no cap */
+    uint32_t wrap_errors;        /* as guber_wire_encode_responses_owner, for every RPC of the pool */
+} guber_wire_mesh_pool_config_t;
+typedef struct guber_wire_mesh_pool_stats {
+    uint64_t rpcs, items, sets;                      /* answered so far (an RPC turned away whole counts as an RPC, not as items) */
+    uint64_t sealed_full, sealed_wait, sealed_idle;  /* why sets left */
+    uint64_t forwarded;                              /* items evaluated on another rank than they arrived at */
+    uint64_t host_rpcs;                              /* RPCs with an item error: marshalled by their CALLER through the host transcoder */
+    uint64_t open_waits;                             /* callers that had to wait for a set to open */
+    uint64_t fill_us_sum, gpu_us_sum;                /* per set: first payload -> sealed; sealed -> answers in host memory */
+} guber_wire_mesh_pool_stats_t;
+int    guber_wire_mesh_pool_create(guber_mesh_t* m, const char* const* owner_addr /* [n_ranks], the ring's peer names */,
+                                   const guber_wire_mesh_pool_config_t* cfg /* NULL = defaults */, guber_wire_mesh_pool_t** out);
+void   guber_wire_mesh_pool_destroy(guber_wire_mesh_pool_t* p);   /* no call may be in flight or arrive any more */
+int    guber_wire_mesh_pool_get_rate_limits(guber_wire_mesh_pool_t* p, uint32_t rank, const uint8_t* req, size_t len,
+                                            uint8_t* resp, size_t cap, size_t* resp_len);
+size_t guber_wire_mesh_pool_response_bound(const guber_wire_mesh_pool_t* p, const uint8_t* req, size_t len);
+int    guber_wire_mesh_pool_set_clock(guber_wire_mesh_pool_t* p, int64_t now_ms);   /* 0 = wall clock; else frozen, as clock.Freeze */
+int    guber_wire_mesh_pool_stats(guber_wire_mesh_pool_t* p, guber_wire_mesh_pool_stats_t* out);
 
 #ifdef __cplusplus
 }

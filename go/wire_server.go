@@ -192,6 +192,23 @@ func NewMeshWireServer(mesh *C.guber_mesh_t, ownerAddr []string) (*MeshWireServe
 	return s, nil
 }
 
+// SetDirect: lone small RPCs evaluated by their handler's own thread (guber_wire_mesh_pool_set_direct) — RPCs of at most maxItems items
+// (0 = off, the default; at most 256) while at most maxCalls calls (0 = 8) are inside the pool take the mesh's one-launch call instead of a
+// stage set.  May be called while the server runs.
+func (s *MeshWireServer) SetDirect(maxItems, maxCalls uint32) error {
+	if rc := C.guber_wire_mesh_pool_set_direct(s.pool, C.uint32_t(maxItems), C.uint32_t(maxCalls)); rc != C.GUBER_OK {
+		return status.Errorf(codes.InvalidArgument, "guber_wire_mesh_pool_set_direct: %s", C.GoString(C.guber_last_error()))
+	}
+	return nil
+}
+
+// DirectStats: RPCs served by their callers so far, and those of them whose small call met a fall-back.
+func (s *MeshWireServer) DirectStats() (direct, fallbacks uint64) {
+	var st C.guber_wire_mesh_pool_direct_stats_t
+	C.guber_wire_mesh_pool_direct_stats(s.pool, &st)
+	return uint64(st.direct_rpcs), uint64(st.fallback_rpcs)
+}
+
 func (s *MeshWireServer) free() {
 	for _, a := range s.addrs {
 		C.free(unsafe.Pointer(a))

@@ -36,7 +36,7 @@ ABI_SYMBOLS = [
     "guber_placement_create", "guber_placement_destroy", "guber_placement_shard", "guber_placement_version", "guber_placement_route_keys",
     "guber_placement_observe", "guber_placement_observe_keys", "guber_placement_rebalance", "guber_placement_info",
     "guber_stages_submit", "guber_stage_poll", "guber_stage_dest", "guber_stage_submit_routed", "guber_placement_plan", "guber_placement_commit", "guber_placement_cancel", "guber_placement_export", "guber_stage_route", "guber_stage_route_poll", "guber_move_items_by_hash", "guber_engine_stream", "guber_pool_global_engine", "guber_pool_global_sync", "guber_pool_rebalance", "guber_pool_get_rate_limits_owner", "guber_pool_add_item", "guber_pool_add_item_for", "guber_pool_load_hinted", "guber_pool_get_item", "guber_pool_size",
-    "guber_mesh_create_local", "guber_mesh_eval_dev", "guber_mesh_eval_rows_dev", "guber_mesh_synchronize", "guber_mesh_stats", "guber_mesh_destroy",
+    "guber_mesh_create_local", "guber_mesh_eval_dev", "guber_mesh_eval_rows_dev", "guber_mesh_eval_small", "guber_mesh_small_stats", "guber_mesh_synchronize", "guber_mesh_stats", "guber_mesh_destroy",
 ]
 
 FLAG_TEST_WEAK_HASH, FLAG_TEST_FORCE_RADIX, FLAG_TEST_CAREFUL, FLAG_GLOBAL, FLAG_DIR_CLAIMS, FLAG_TEST_NO_SMALL = 1, 2, 4, 8, 16, 32
@@ -985,4 +985,4 @@ class V1Instance:
             pass
 
 
-from .mesh import Mesh, MeshRows, MeshStats  # noqa: E402,F401  (guber_mesh_*: a stream that crosses ranks)
+from .mesh import Mesh, MeshRows, MeshSmallStats, MeshStats  # noqa: E402,F401  (guber_mesh_*: a stream that crosses ranks)

@@ -14,6 +14,16 @@ static int small_prelude(guber_engine* e, const BatchView& B) {
     e->batches++; e->small_batches++;
     return 0;
 }
+// the counters of a completed one-launch batch that did not fall back, into the host's image (eval_host_once, guber_mesh_eval_small)
+static void small_fold(guber_engine* e, const SmallOut* sout) {
+    // a snapshot launched ahead of this batch (small_prelude's maintain, near the cache's size) is older than what is added here:
+    // folded now, not by the maintain() behind the batch — that one would put the counters back to before the batch
+    if (rb_any_armed(e)) {
+        rb_fold_newest(e);
+        for (uint32_t i = 0; i < guber_engine::kRb; ++i) if ((int)i != e->rb_ride) e->rb[i].armed = false;   // (launched ahead of this batch: none may be folded behind it)
+    }
+    e->last_ctr.over += sout->over; e->last_ctr.hits += sout->hits; e->last_ctr.misses += sout->misses; e->last_ctr.size += sout->size_delta;
+}
 static int launch_small(guber_engine* e, const BatchView& B, const ResultView& R, SmallOut* out, uint32_t seq) {
     const int rc = small_prelude(e, B);
     if (rc) return rc;
@@ -97,16 +107,8 @@ static int eval_host_once(guber_engine* e, const guber_batch_t* b, guber_result_
             while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) {
                 if ((++spins & 0x3ff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) { HIPCHK(hipStreamSynchronize(st)); break; }
             }
-            if (!sout->fallback) {
-                // a snapshot launched ahead of this batch (small_prelude's maintain, near the cache's size) is older than what is added here:
-                // folded now, not by the maintain() behind the batch — that one would put the counters back to before the batch
-                if (rb_any_armed(e)) {
-                    rb_fold_newest(e);
-                    for (uint32_t i = 0; i < guber_engine::kRb; ++i) if ((int)i != e->rb_ride) e->rb[i].armed = false;   // (launched ahead of this batch: none may be folded behind it)
-                }
-                e->last_ctr.over += sout->over; e->last_ctr.hits += sout->hits; e->last_ctr.misses += sout->misses; e->last_ctr.size += sout->size_delta;
-                done = true;
-            } else e->small_fallbacks++;
+            if (!sout->fallback) { small_fold(e, sout); done = true; }
+            else e->small_fallbacks++;
         }
         if (!done) {
             rc = launch_batch(e, B, R, true);

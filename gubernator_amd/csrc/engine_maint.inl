@@ -251,3 +251,4 @@ extern "C" const char* guber_last_error(void) { return g_last_error.c_str(); }
 #include "guber_wire_pool.h"    // guber_wire_pool_*: the payload stage (caller threads hand over serialized RPCs)
 #include "guber_wire_pool_peer.h"   // guber_wire_pool_update_peer_globals: a broadcast of GLOBAL buckets installed through the pool's rule
 #include "guber_wire_mesh_pool.h"   // guber_wire_mesh_pool_*: the payload stage over a mesh (RPC bytes in at any rank, response bytes out)
+#include "guber_wire_mesh_pool_direct.h"   // ... and its lone small RPCs evaluated by their caller (guber_wire_mesh_pool_set_direct)

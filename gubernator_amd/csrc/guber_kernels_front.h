@@ -148,6 +148,17 @@ __device__ __forceinline__ void route_scan(const RouteMap& M, uint32_t seq, uint
     }
 }
 
+// The front's rule for one request, k_fr_count's and k_mx_small's (guber_kernels_small.h) alike, in ONE place.  A macro, not a function:
+// k_fr_count's instruction stream is part of what the benchmark measures, and the statements below are the ones it has always had — a
+// function taking the hash as a callable compiled to another stream.  E = the engine of request I with a key of LEN bytes (HASH: the
+// expression of its XXH64, evaluated only when the rule looks at it).  A key no engine takes (empty, above MAX_KEY) goes to engine 0
+// and earns its item error there.
+#define FR_ENGINE(E, R, N_ENGINES, MAX_KEY, BEHAVIOR, I, LEN, HASH)                                                                         \
+    E = 0;                                                                                                                                  \
+    if ((R).global_engine >= 0 && (BEHAVIOR) && ((BEHAVIOR)[I] & 2u)) E = (uint32_t)(R).global_engine;   /* Behavior_GLOBAL: the device's GLOBAL engine */ \
+    else if ((LEN) != 0 && (LEN) <= (MAX_KEY) && (R).n_shards > 1) E = route_engine((R), (HASH));                                           \
+    if (E >= (N_ENGINES)) E = 0;
+
 __global__ __launch_bounds__(FR_TILE) void k_fr_count(FrIn A) {
     // one request per thread, 1 024 threads: the chain offsets -> key -> hot-key list -> slot table is four dependent trips, and what hides
     // them is waves in flight (four requests per thread, a quarter of the waves: 24 us instead of 20 for a million requests)
@@ -165,13 +176,10 @@ __global__ __launch_bounds__(FR_TILE) void k_fr_count(FrIn A) {
         // (a packed buffer is readable 8 bytes past the last key; of a row, its key_stride bytes)
         const bool spec = key_fetch_spec(A.key_bytes, off_g, len0, A.key_stride ? (uint64_t)off_g + A.key_stride : (uint64_t)oend + 8, kw);
         const uint32_t off = fr_key_off(A, i), len = fr_key_len(A, i, off);
-        e = 0;
         // (the hash is not handed on to k_part: a column for it costs the copy kernels 32 B per request, measured -2 % on the routed rate with
         //  k_part hashing less — the pipeline is closer to its transactions than to its instructions: profiles/r06_pass_hash_ab.txt)
-        if (A.R.global_engine >= 0 && A.behavior && (A.behavior[i] & 2u)) e = (uint32_t)A.R.global_engine;      // Behavior_GLOBAL: the device's GLOBAL engine
-        else if (len != 0 && len <= A.max_key && A.R.n_shards > 1)
-            e = route_engine(A.R, (spec && off == off_g && len == len0) ? xxhash64_words4_uniform(kw, len0, 0) : xxhash64(A.key_bytes + off, len, 0));
-        if (e >= A.n_engines) e = 0;
+        FR_ENGINE(e, A.R, A.n_engines, A.max_key, A.behavior, i, len,
+                  (spec && off == off_g && len == len0) ? xxhash64_words4_uniform(kw, len0, 0) : xxhash64(A.key_bytes + off, len, 0))
         if (len != len0 || off != off_g || len0 == 0 || len0 > FR_KEY_COPY_MAX) {
             if (__hip_atomic_load(&A.M.ctl->ragged_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != A.seq) atomicExch(&A.M.ctl->ragged_seq, A.seq);
         }

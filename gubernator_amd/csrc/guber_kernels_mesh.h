@@ -71,6 +71,32 @@ __device__ __forceinline__ uint64_t mx_fnv_words4(const uint64_t (&w)[4], uint32
     return h;
 }
 
+// The decision per request, k_mx_count's and k_mx_small's (guber_kernels_small.h) alike, in ONE place.  A macro, not a function: k_mx_count's
+// instruction stream is part of what the benchmark measures, and the statements below are the ones it has always had — a function taking
+// the hash as a callable compiled to another stream.  For a request that arrived at rank SELF with a key of LEN bytes (HASH: the expression
+// of its fnv1 / fnv1a, evaluated only when the key is not over-long; GLOBAL: Behavior_GLOBAL is set) it declares
+//   stay   the request is not forwarded: GLOBAL (gubernator.go:258-270), or a key the ring cannot place (empty, above MAX_KEY)
+//   owner  the ring's peer for the key — ReplicatedConsistentHash.Get (replicated_hash.go:104-119): the first point at or behind the key's
+//          hash, wrapping to point 0 (an over-long key is not hashed: nobody looks at the owner of a request that only earns its item error)
+// and MX_EVAL_RANK / MX_IS_OWNER / MX_ITEM_OWNER below say what follows from the two.
+#define MX_DECIDE(stay, owner, GLOBAL, LEN, SELF, MAX_KEY, NPTS, LH, RING_OWNER, HASH)                                                     \
+    const bool stay = (GLOBAL) || (LEN) == 0 || (LEN) > (MAX_KEY);                                                                        \
+    uint32_t owner = (SELF);                                                                                                              \
+    if ((LEN) <= (MAX_KEY)) {                                                                                                             \
+        const uint64_t h = (HASH);                                                                                                        \
+        uint32_t lo = 0, hi = (NPTS);                                                                                                     \
+        while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if ((LH)[mid] >= h) hi = mid; else lo = mid + 1; }                  \
+        if (lo == (NPTS)) lo = 0;                                                                                                         \
+        owner = (RING_OWNER)[lo];                                                                                                         \
+    }
+// the rank that evaluates the request
+#define MX_EVAL_RANK(stay, owner, SELF, WORLD) ((stay) || (owner) >= (WORLD) ? (SELF) : (owner))
+// the is_owner it is evaluated with (forwarded or owned here: evaluated as the owner, gubernator.go:247-256, :486)
+#define MX_IS_OWNER(stay, owner, SELF) ((stay) ? (uint8_t)((owner) == (SELF)) : (uint8_t)1)
+// who the ring names, for the caller that tells its client (metadata "owner", gubernator.go:267-268, :379-381): a GLOBAL request's too,
+// although it stays; a key the ring cannot place (empty, over-long) has none
+#define MX_ITEM_OWNER(LEN, MAX_KEY, owner) (((LEN) == 0 || (LEN) > (MAX_KEY)) ? (uint8_t)0xffu : (uint8_t)(owner))
+
 template <bool ROWS> __global__ __launch_bounds__(FR_TILE) void k_mx_count(MxIn A) {
     GUBER_DYN_LDS(smem);                                             // the ring's hashes (npts x 8 bytes) when they fit beside route_rank_tile's 1 KB
     const uint32_t tid = threadIdx.x, i = blockIdx.x * FR_TILE + tid;
@@ -95,23 +121,13 @@ template <bool ROWS> __global__ __launch_bounds__(FR_TILE) void k_mx_count(MxIn 
             off = (uint32_t)off_g; len = A.key_len[i];
             if (len > A.key_stride) len = A.max_key + 1u;            // (more than a row holds: over-long, never read)
         } else { off = A.key_off[i]; len = A.key_off[i + 1] - off; }
-        const bool stay = (A.behavior && (A.behavior[i] & 2u)) || len == 0 || len > A.max_key;
-        // ReplicatedConsistentHash.Get (replicated_hash.go:104-119): the first point at or behind the key's hash, wrapping to point 0
-        // (an over-long key is not hashed: nobody looks at the owner of a request that only earns its item error)
-        uint32_t owner = A.self;
-        if (len <= A.max_key) {
-            const uint64_t h = (spec && off == off_g && len == len0) ? mx_fnv_words4(kw, len, A.kind)
-                                                                    : (A.kind == 1 ? fnv1a_64(A.key_bytes + off, len) : fnv1_64(A.key_bytes + off, len));
-            uint32_t lo = 0, hi = A.npts;
-            while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (lh[mid] >= h) hi = mid; else lo = mid + 1; }
-            if (lo == A.npts) lo = 0;
-            owner = A.ring_owner[lo];
-        }
-        e = stay || owner >= A.world ? A.self : owner;
-        A.own[i] = stay ? (uint8_t)(owner == A.self) : (uint8_t)1;   // (forwarded or owned here: evaluated as the owner, gubernator.go:247-256, :486)
-        // who the ring names, for the caller that tells its client (metadata "owner", gubernator.go:267-268, :379-381): a GLOBAL request's too,
-        // although it stays; a key the ring cannot place (empty, over-long) has none.  As d_fwd in the front: stored only when wanted.
-        if (A.item_owner) A.item_owner[i] = (len == 0 || len > A.max_key) ? (uint8_t)0xffu : (uint8_t)owner;
+        MX_DECIDE(stay, owner, A.behavior && (A.behavior[i] & 2u), len, A.self, A.max_key, A.npts, lh, A.ring_owner,
+                  (spec && off == off_g && len == len0) ? mx_fnv_words4(kw, len, A.kind)
+                                                        : (A.kind == 1 ? fnv1a_64(A.key_bytes + off, len) : fnv1_64(A.key_bytes + off, len)))
+        e = MX_EVAL_RANK(stay, owner, A.self, A.world);
+        A.own[i] = MX_IS_OWNER(stay, owner, A.self);
+        // As d_fwd in the front: stored only when wanted.
+        if (A.item_owner) A.item_owner[i] = MX_ITEM_OWNER(len, A.max_key, owner);
     }
     route_rank_tile(e, A.M, i, A.n);
 }

@@ -277,4 +277,76 @@ __global__ __launch_bounds__(FT) void k_small_routed(MultiSmallRouted A) {
     small_body(a->T, B, A.R, a->out, a->seq, a->touch, map);
 }
 
+// The one-launch path of a MESH of fronts (guber_mesh_eval_small, guber_mesh.h): a call of at most one tile over all ranks together.  The
+// requests lie in ONE arena of host memory every rank's device sees — request columns, packed keys, source rank after source rank in
+// arrival order, src_start[W + 1] — and every rank gets one launch, one workgroup per engine of its front.  The workgroup of rank `self`,
+// engine blockIdx.x takes, per request t of source s, the decision k_mx_count takes (MX_DECIDE: with source s's max_key_bytes, on the
+// ring arrays of this rank's device) and, for the requests this rank evaluates, the front's rule as k_fr_count applies it (FR_ENGINE: the
+// rule as the front holds it on the device); it compacts its own stably — ascending t is source 0, 1, ... W-1, each in arrival order:
+// the mesh's order rule — and runs the one-launch body on them in place.  The taker of request t, and nobody else, writes where[t] =
+// evaluating rank | engine << 8 | item_owner << 16 and the is_owner the request is evaluated with (B.is_owner points at that column: the
+// body reads it behind the workgroup's barrier), and every workgroup leaves its share's size in taken[engine].  A workgroup without a
+// share touches no table and reports done.  No tickets, no scratch.  The host guarantees n_total <= FT and an ascending src_start.
+struct MxSmallSub { Table T; SmallOut* out; uint64_t touch; uint32_t seq, pad_; };
+struct MxSmall {
+    uint32_t n_total, self, world, n_engines, npts, kind, front_max_key, pad_;
+    const uint32_t* src_start;                                       // the arena's: [world + 1]
+    const uint32_t* src_max_key;                                     // device memory: [world] the ranks' max_key_bytes
+    const uint64_t* ring_hash; const uint8_t* ring_owner;            // this rank's device
+    BatchView B; ResultView R;                                       // the arena's columns, n_total requests; B.is_owner = own
+    uint32_t* where; uint8_t* own;
+    uint32_t* taken;                                                 // the arena's: [n_engines] of this rank — the shares' sizes, for the host's check of where[]
+    RouteRule rule;
+    MxSmallSub sub[MULTI_MEM_MAX];
+};
+static_assert(sizeof(MxSmall) <= 4096, "kernel arguments are limited to 4 KB");
+__global__ __launch_bounds__(FT) void k_mx_small(MxSmall A) {
+    __shared__ uint32_t map[FT];
+    __shared__ uint32_t wtot[FT / 64];
+    const MxSmallSub* a = (const MxSmallSub*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(MxSmall, sub)) + blockIdx.x;
+    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    // (src_start lies in host memory: read once per workgroup, not once per thread and step)
+    __shared__ uint32_t sstart[MULTI_MEM_MAX + 1];
+    if (t <= A.world && t <= (uint32_t)MULTI_MEM_MAX) sstart[t] = A.src_start[t];
+    __syncthreads();
+    bool mine = false;
+    if (t < A.n_total) {
+        uint32_t s = 0;
+        while (s + 1 < A.world && sstart[s + 1] <= t) ++s;
+        const uint32_t off = A.B.key_off[t], len = A.B.key_off[t + 1] - off;
+        MX_DECIDE(stay, owner, (A.B.behavior[t] & 2u) != 0, len, s, A.src_max_key[s], A.npts, A.ring_hash, A.ring_owner,
+                  A.kind == 1 ? fnv1a_64(A.B.key_bytes + off, len) : fnv1_64(A.B.key_bytes + off, len))
+        const uint32_t rank = MX_EVAL_RANK(stay, owner, s, A.world);
+        if (rank == A.self) {
+            uint32_t eng;
+            FR_ENGINE(eng, A.rule, A.n_engines, A.front_max_key, A.B.behavior, t, len, xxhash64(A.B.key_bytes + off, len, 0))
+            mine = eng == blockIdx.x;
+            if (mine) {
+                A.where[t] = rank | eng << 8 | (uint32_t)MX_ITEM_OWNER(len, A.src_max_key[s], owner) << 16;
+                A.own[t] = MX_IS_OWNER(stay, owner, s);
+            }
+        }
+    }
+    const unsigned long long m = __ballot(mine);
+    if (lane == 0) wtot[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t before = 0, share = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < FT / 64; ++w) { if (w < wave) before += wtot[w]; share += wtot[w]; }
+    if (mine) map[before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = t;
+    __syncthreads();
+    if (t == 0) A.taken[blockIdx.x] = share;                         // (visible with the flag: thread 0 releases it)
+    if (share == 0) {
+        if (t == 0) {
+            a->out->fallback = 0u; a->out->over = a->out->hits = a->out->misses = 0u; a->out->size_delta = 0;
+            __threadfence_system();
+            __hip_atomic_store(&a->out->done, a->seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        return;
+    }
+    BatchView B = A.B;
+    B.n = share;
+    small_body(a->T, B, A.R, a->out, a->seq, a->touch, map);
+}
+
 }  // namespace guber

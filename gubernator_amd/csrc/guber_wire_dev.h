@@ -612,6 +612,10 @@ extern "C" int guber_wire_dev_eval_mesh_enc(guber_wire_dev_t* const* decs, guber
 // decoder's HBM once and for all (buffers for the decoder's largest decode: no call of the pool allocates), and one set's way from its
 // collected decodes to "the device is done" (*forwarded: the items it moved to another rank)
 static void wire_mesh_pool_shape(guber_mesh_t* m, uint32_t* W, uint32_t* max_n) { *W = m->W; *max_n = m->max_n; }
+// the mesh's one-launch call for the pool's direct path (guber_wire_mesh_pool_direct.h), with the call's own forwarded and fall-back counts
+static int wire_mesh_pool_eval_small(guber_mesh_t* m, const guber_batch_t* gens, guber_result_t* results, uint8_t* const* owner_rank, uint64_t* forwarded, uint64_t* fallbacks) {
+    return mesh_eval_small_counted(m, gens, results, owner_rank, forwarded, fallbacks);
+}
 static guber_engine_t* wire_mesh_pool_engine(guber_mesh_t* m, uint32_t r, uint32_t* max_batch) { guber_engine* e = m->ranks[r].f->eng[0]; *max_batch = e->max_batch; return e; }
 static int wire_mesh_pool_prepare(guber_wire_dev* d, const WireMeshSfx& T) {
     guber_engine* e = d->e;

@@ -23,6 +23,8 @@
 //                    guber_wire_pool's reservation word: a place here is three counters of one of W stages plus the set's own, which one
 //                    compare-and-swap does not cover, and the mesh call behind it is host-bound at ~1 ms (profiles/mesh_first_numbers.txt) —
 //                    a mutex held for a few dozen instructions per RPC is not what limits it.  Correctness first.
+//   direct path      opt-in (guber_wire_mesh_pool_set_direct): a lone small RPC that arrives while few calls are inside joins no set — its caller
+//                    evaluates it through the mesh's one-launch call.  guber_wire_mesh_pool_direct.h, reached through `direct` alone.
 #pragma once
 #include <condition_variable>
 #include <deque>
@@ -55,6 +57,13 @@ struct guber_wire_mesh_pool {
     bool stop = false, closed = false, failed = false;                  // closed: no caller is let in any more; failed: a set failed on the devices
     std::atomic<int64_t> clock_ms{0};
     std::thread dispatcher;
+    // the direct path (guber_wire_mesh_pool_direct.h, included behind this file; guber_wire_mesh_pool_set_direct fills `direct`): a lone small RPC
+    // evaluated by its caller.  direct_items: the largest item bound that takes it (0 = off, the default); direct_calls: the most calls
+    // that may be inside the pool for an RPC to take it; inside: calls past the door, on either path
+    typedef int (*DirectFn)(guber_wire_mesh_pool*, uint32_t rank, const uint8_t* req, size_t len, guber_wire_batch_t* wb, uint8_t* resp, size_t cap, size_t* resp_len);
+    std::atomic<DirectFn> direct{nullptr};
+    std::atomic<uint32_t> direct_items{0}, direct_calls{8}, inside{0};
+    std::atomic<uint64_t> st_direct{0}, st_direct_fallback{0};
     std::atomic<uint64_t> st_rpcs{0}, st_items{0}, st_sets{0}, st_full{0}, st_wait{0}, st_idle{0}, st_forwarded{0}, st_host_rpcs{0}, st_open_waits{0}, st_fill_us{0}, st_gpu_us{0};
 };
 
@@ -259,6 +268,12 @@ extern "C" int guber_wire_mesh_pool_get_rate_limits(guber_wire_mesh_pool_t* p, u
     const uint32_t bound = std::max(1u, wpl_item_bound(req, len, p->item_cap));
     thread_local MplThreadBatch tl;
     if (tl.ensure(bound, len + bound + 16)) return fail(GUBER_E_NOMEM, "guber_wire_mesh_pool: no memory for the host transcoder's batch");
+    struct Inside { MP* p; uint32_t n; explicit Inside(MP* q) : p(q), n(q->inside.fetch_add(1, std::memory_order_acq_rel) + 1) {} ~Inside() { p->inside.fetch_sub(1, std::memory_order_acq_rel); } } in(p);
+    // ---- a lone small RPC while few calls are inside: its caller evaluates it (off unless guber_wire_mesh_pool_set_direct switched it on)
+    if (const uint32_t di = p->direct_items.load(std::memory_order_acquire)) {
+        const MP::DirectFn fn = p->direct.load(std::memory_order_acquire);
+        if (fn && bound <= di && in.n <= p->direct_calls.load(std::memory_order_relaxed)) return fn(p, rank, req, len, tl.wb, resp, cap, resp_len);
+    }
     // ---- a place in rank's stage of the open set
     MP::Set* sp = nullptr;
     uint32_t idx = 0; size_t off = 0; uint64_t seq = 0;

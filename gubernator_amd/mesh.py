@@ -11,6 +11,10 @@ class MeshStats(C.Structure):
                 ("inflow_pieces", C.c_uint64), ("ms", C.c_double)]
 
 
+class MeshSmallStats(C.Structure):
+    _fields_ = [("calls", C.c_uint64), ("launches", C.c_uint64), ("wholesale_fallbacks", C.c_uint64), ("share_fallbacks", C.c_uint64)]
+
+
 class MeshRows(C.Structure):
     """guber_mesh_rows_t: key_stride 0 = the rank's generation is packed; otherwise its keys lie in rows key_stride bytes apart (a
     multiple of 8) and key_len is a device array of the keys' lengths"""
@@ -27,6 +31,8 @@ def _lib():
         L.guber_mesh_create_local.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
         L.guber_mesh_eval_dev.argtypes = [C.c_void_p, C.POINTER(GuberBatch), C.POINTER(GuberResult)]
         L.guber_mesh_eval_rows_dev.argtypes = [C.c_void_p, C.POINTER(GuberBatch), C.POINTER(MeshRows), C.POINTER(GuberResult)]
+        L.guber_mesh_eval_small.argtypes = [C.c_void_p, C.POINTER(GuberBatch), C.POINTER(GuberResult), C.POINTER(C.c_void_p)]
+        L.guber_mesh_small_stats.argtypes = [C.c_void_p, C.POINTER(MeshSmallStats)]
         L.guber_mesh_synchronize.argtypes = [C.c_void_p]
         L.guber_mesh_stats.argtypes = [C.c_void_p, C.POINTER(MeshStats)]
         L.guber_mesh_destroy.argtypes = [C.c_void_p]
@@ -59,6 +65,17 @@ class Mesh:
         """eval_dev for generations whose keys lie in rows: `rows` a ctypes array of len(fronts) MeshRows (None: every rank packed); rank
         r with rows[r].key_stride != 0 has gens[r].key_bytes = its first row and gens[r].key_off = None"""
         _check(_lib().guber_mesh_eval_rows_dev(self.h, gens, rows, results))
+
+    def eval_small(self, gens, results, owner_rank=None):
+        """the one-launch path for a call of at most 256 requests over all ranks (guber_mesh_eval_small): ctypes arrays of len(fronts)
+        GuberBatch / GuberResult of HOST pointers; owner_rank: None, or a ctypes array of len(fronts) c_void_p (None, or gens[r].n bytes
+        that receive the ring's owner of every item, 0xFF = none).  Synchronous: the answers are complete on return"""
+        _check(_lib().guber_mesh_eval_small(self.h, gens, results, owner_rank))
+
+    def small_stats(self):
+        st = MeshSmallStats()
+        _check(_lib().guber_mesh_small_stats(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in MeshSmallStats._fields_}
 
     def synchronize(self):
         _check(_lib().guber_mesh_synchronize(self.h))

@@ -24,7 +24,7 @@ WIRE_SYMBOLS = [
     "guber_wire_pool_get_peer_rate_limits", "guber_wire_pool_update_peer_globals",
     "guber_wire_pool_set_clock", "guber_wire_pool_stats",
     "guber_wire_mesh_pool_create", "guber_wire_mesh_pool_destroy", "guber_wire_mesh_pool_get_rate_limits", "guber_wire_mesh_pool_response_bound",
-    "guber_wire_mesh_pool_set_clock", "guber_wire_mesh_pool_stats",
+    "guber_wire_mesh_pool_set_clock", "guber_wire_mesh_pool_stats", "guber_wire_mesh_pool_set_direct", "guber_wire_mesh_pool_direct_stats",
 ]
 _bound = False
 
@@ -508,6 +508,8 @@ class WireMeshPool:
         L.guber_wire_mesh_pool_response_bound.restype = C.c_size_t
         L.guber_wire_mesh_pool_set_clock.argtypes = [C.c_void_p, C.c_int64]
         L.guber_wire_mesh_pool_stats.argtypes = [C.c_void_p, C.POINTER(WireMeshPoolStats)]
+        L.guber_wire_mesh_pool_set_direct.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+        L.guber_wire_mesh_pool_direct_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64 * 2)]
         self._stats = WireMeshPoolStats
         self.mesh = mesh
         self.addrs, arr = _addr_array(owner_addr)
@@ -549,6 +551,18 @@ class WireMeshPool:
         st = self._stats()
         self.L.guber_wire_mesh_pool_stats(self._open(), C.byref(st))
         return {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+    def set_direct(self, max_items, max_calls=0):
+        """lone small RPCs evaluated by their caller (guber_wire_mesh_pool_set_direct): RPCs of at most max_items items (0 = off, the
+        default; <= 256) while at most max_calls calls (0 = 8) are inside the pool go through Mesh.eval_small's call instead of a set"""
+        rc = self.L.guber_wire_mesh_pool_set_direct(self._open(), max_items, max_calls)
+        if rc:
+            raise GuberError(rc, lib().guber_last_error().decode())
+
+    def direct_stats(self):
+        st = (C.c_uint64 * 2)()
+        self.L.guber_wire_mesh_pool_direct_stats(self._open(), C.byref(st))
+        return dict(direct_rpcs=int(st[0]), fallback_rpcs=int(st[1]))
 
     def close(self):
         if getattr(self, "h", None):

@@ -821,6 +821,34 @@ typedef struct guber_mesh_rows { uint32_t key_stride; const uint32_t* key_len; }
 int guber_mesh_eval_rows_dev(guber_mesh_t* m, const guber_batch_t* gens /* [n_ranks] */,
                              const guber_mesh_rows_t* rows /* [n_ranks], NULL = every rank packed */,
                              guber_result_t* results /* [n_ranks] */);
+/* guber_mesh_eval_small: the ONE-LAUNCH path for a small call — at most 256 requests over all ranks together — from HOST memory, and
+ * SYNCHRONOUS: gens[r] is what arrived at rank r (host pointers, packed keys; is_owner, greg_expire and greg_duration NULL; burst and
+ * created_at optional; one now_ms for all), results[r] host arrays of gens[r].n entries, complete on return.  The answers, the residency,
+ * the order across sources and the `calls` / `requests` / `forwarded` statistics are those of guber_mesh_eval_dev for the same generations;
+ * guber_stats of every engine moves as it does there.  owner_rank (optional): owner_rank[r] NULL or gens[r].n bytes — the peer the RING
+ * names for item i (not where it was evaluated), 0xFF where the ring places no key (empty, over-long).
+ *   how           the generations are copied into one pinned arena every rank's device sees; every rank gets one launch with one
+ *                 workgroup per engine of its front (k_mx_small), which takes the ring's and the front's decisions ON THE DEVICE — the
+ *                 rule is the one guber_front_set_rule left there — picks its share in the order rule's order and evaluates it in place;
+ *                 the host polls the shares' completion words.  n_ranks == 1 works: the front alone.
+ *   refusals      more than 256 requests in all: GUBER_E_BATCH_TOO_LARGE; every refusal of guber_mesh_eval_dev applies; all of them come
+ *                 before anything is enqueued and before an engine is looked at.  (An error later — a HIP call, an engine's maintenance
+ *                 before the launch — is no refusal: engines may have done their maintenance; no launch is left running on return.)
+ *   fall-backs    the call always answers.  WHOLESALE, before any launch: when an engine of any rank cannot take the one-launch path (its
+ *                 bounded cache may bind for the call's total, a test flag keeps it off it, its front holds a probed or pre-routed
+ *                 generation) the call goes through guber_mesh_eval_dev's path on small device buffers of the mesh's own.  PER SHARE,
+ *                 after the launch: a share the kernel declines (requests of one key that differ, a 64-bit hash collision — nothing of
+ *                 it was evaluated) is re-run on its engine through the general pipeline; the other shares stand, and since the shares of
+ *                 different engines hold disjoint keys the order rule is untouched.
+ *   one box       the arena is allocated portable across devices; a kernel on one GPU reading what another rank's caller wrote through
+ *                 it cannot be exercised with every rank on one device, which is all the tests have.
+ * guber_mesh_small_stats: calls = guber_mesh_eval_small calls that held a request, launches = k_mx_small launches (one per rank of a call
+ * that took the path), wholesale_fallbacks = calls that went the general way, share_fallbacks = shares re-run. */
+typedef struct guber_mesh_small_stats { uint64_t calls, launches, wholesale_fallbacks, share_fallbacks; } guber_mesh_small_stats_t;
+int guber_mesh_eval_small(guber_mesh_t* m, const guber_batch_t* gens /* [n_ranks], HOST pointers */,
+                          guber_result_t* results /* [n_ranks], HOST arrays */,
+                          uint8_t* const* owner_rank /* optional: [n_ranks] -> [gens[r].n], 0xFF = none */);
+int guber_mesh_small_stats(guber_mesh_t* m, guber_mesh_small_stats_t* out);
 int guber_mesh_synchronize(guber_mesh_t* m);
 int guber_mesh_stats(guber_mesh_t* m, guber_mesh_stats_t* out);
 void guber_mesh_destroy(guber_mesh_t* m);

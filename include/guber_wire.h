@@ -367,8 +367,7 @@ int guber_wire_pool_stats(guber_wire_pool_t* p, guber_wire_pool_stats_t* out);
  *   Other threads may keep calling guber_mesh_eval*, guber_add_items and guber_global_sync on the same objects: the mesh's and the engines' locks
  *   serialise them, as beside guber_wire_pool.
  *   What this surface does NOT do: GetPeerRateLimits / UpdatePeerGlobals (every peer of the mesh's ring is a local rank, nobody outside sends
- *   them; guber_wire_pool serves them per device), the Store callbacks, a caller-evaluated fast path for a lone small RPC (guber_wire_pool's
- *   has no counterpart here yet), non-blocking dispatch (the dispatcher waits for the GPUs phase by phase), an RCCL transport and one rank per
+ *   them; guber_wire_pool serves them per device), the Store callbacks, non-blocking dispatch (the dispatcher waits for the GPUs phase by phase), an RCCL transport and one rank per
  *   process (guber_mesh_create_local's ranks live in this process). */
 typedef struct guber_wire_mesh_pool guber_wire_mesh_pool_t;
 typedef struct guber_wire_mesh_pool_config {
@@ -396,6 +395,20 @@ int    guber_wire_mesh_pool_get_rate_limits(guber_wire_mesh_pool_t* p, uint32_t 
 size_t guber_wire_mesh_pool_response_bound(const guber_wire_mesh_pool_t* p, const uint8_t* req, size_t len);
 int    guber_wire_mesh_pool_set_clock(guber_wire_mesh_pool_t* p, int64_t now_ms);   /* 0 = wall clock; else frozen, as clock.Freeze */
 int    guber_wire_mesh_pool_stats(guber_wire_mesh_pool_t* p, guber_wire_mesh_pool_stats_t* out);
+/* Lone small RPCs evaluated by their CALLER (opt-in; off by default, and with it off the pool behaves exactly as without it).  A stage set
+ * costs a lone one-item RPC a decode, the mesh's general call, an encoder and the dispatcher's waits.  With max_items != 0 an RPC whose item
+ * bound is at most max_items (<= 256), arriving while at most max_calls calls (0 = 8) are inside the pool and the pool is open, joins no set:
+ * its caller decodes it with the host transcoder at the pool's clock, evaluates it with guber_mesh_eval_small (include/guber_gpu.h: one
+ * launch per rank; the ring's and the fronts' decisions are taken on the devices, as in a set) and writes the bytes
+ * guber_wire_encode_responses_owner writes — error texts and metadata{"owner"} included.  Everything a set checks at the door applies
+ * unchanged (malformed and too large messages, a cap below the bound, len == 0), with the same codes.  The call is synchronous under the
+ * mesh's mutex: a call that has returned was evaluated before any call that starts later, on either path.  max_items = 0 switches the path
+ * off again.  May be called while callers are inside.
+ * guber_wire_mesh_pool_direct_stats: direct_rpcs = RPCs served this way (they count in stats.rpcs / items / forwarded, in no set);
+ * fallback_rpcs = those of them whose small call met a fall-back of either kind (guber_mesh_small_stats). */
+typedef struct guber_wire_mesh_pool_direct_stats { uint64_t direct_rpcs, fallback_rpcs; } guber_wire_mesh_pool_direct_stats_t;
+int    guber_wire_mesh_pool_set_direct(guber_wire_mesh_pool_t* p, uint32_t max_items /* 0 = off */, uint32_t max_calls /* 0 = 8 */);
+int    guber_wire_mesh_pool_direct_stats(guber_wire_mesh_pool_t* p, guber_wire_mesh_pool_direct_stats_t* out);
 
 #ifdef __cplusplus
 }

@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "guber_placement_observe", "guber_placement_observe_keys", "guber_placement_rebalance", "guber_placement_info",
     "guber_stages_submit", "guber_stage_poll", "guber_stage_dest", "guber_stage_submit_routed", "guber_placement_plan", "guber_placement_commit", "guber_placement_cancel", "guber_placement_export", "guber_stage_route", "guber_stage_route_poll", "guber_move_items_by_hash", "guber_engine_stream", "guber_pool_global_engine", "guber_pool_global_sync", "guber_pool_rebalance", "guber_pool_get_rate_limits_owner", "guber_pool_add_item", "guber_pool_add_item_for", "guber_pool_load_hinted", "guber_pool_get_item", "guber_pool_size",
     "guber_mesh_create_local", "guber_mesh_eval_dev", "guber_mesh_eval_rows_dev", "guber_mesh_eval_small", "guber_mesh_small_stats", "guber_mesh_synchronize", "guber_mesh_stats", "guber_mesh_destroy",
+    "guber_placement_observe_aggregate", "guber_front_observe", "guber_front_observation", "guber_front_rebalance",
 ]
 
 FLAG_TEST_WEAK_HASH, FLAG_TEST_FORCE_RADIX, FLAG_TEST_CAREFUL, FLAG_GLOBAL, FLAG_DIR_CLAIMS, FLAG_TEST_NO_SMALL = 1, 2, 4, 8, 16, 32
@@ -228,6 +229,42 @@ class Placement:
 
     def observe_keys(self, key_bytes, key_off):
         _check(lib().guber_placement_observe_keys(self.h, key_bytes.ctypes.data, key_off.ctypes.data, len(key_off) - 1))
+
+    def observe(self, key_hash, weight=1):
+        L = lib()
+        L.guber_placement_observe.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32]
+        L.guber_placement_observe.restype = None
+        L.guber_placement_observe(self.h, int(key_hash), int(weight))
+
+    def observe_aggregate(self, slot_w, hashes=(), counts=()):
+        """guber_placement_observe_aggregate: requests per slot (uint32[n_slots], the candidates' among them) and the keys that may be
+        heavy with their counts (they go to the heavy-hitter sketch only)"""
+        L = lib()
+        L.guber_placement_observe_aggregate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
+        sw = np.ascontiguousarray(slot_w, np.uint32)
+        hh, cc = np.ascontiguousarray(hashes, np.uint64), np.ascontiguousarray(counts, np.uint32)
+        assert len(hh) == len(cc)
+        _check(L.guber_placement_observe_aggregate(self.h, sw.ctypes.data, len(sw), hh.ctypes.data, cc.ctypes.data, len(hh)))
+
+    def plan(self, heavy_fraction=0.125):
+        """guber_placement_plan -> list of (key_hash, from, to); commit() publishes it"""
+        L = lib()
+        L.guber_placement_plan.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        mv = np.zeros(64 * 4, np.uint32)
+        nm = C.c_uint32(0)
+        _check(L.guber_placement_plan(self.h, heavy_fraction, mv.ctypes.data, 64, C.byref(nm)))
+        rec = mv.view(np.dtype([("h", np.uint64), ("from", np.uint32), ("to", np.uint32)]))
+        return [(int(r["h"]), int(r["from"]), int(r["to"])) for r in rec[:nm.value]]
+
+    def commit(self):
+        L = lib()
+        L.guber_placement_commit.argtypes = [C.c_void_p]
+        _check(L.guber_placement_commit(self.h))
+
+    def n_slots(self):
+        ns = C.c_uint32(0)
+        _check(lib().guber_placement_info(self.h, None, C.byref(ns), None))
+        return ns.value
 
     def rebalance(self, heavy_fraction=0.125, move_slots=True):
         """-> list of (key_hash, from, to) for the hot keys whose shard changed"""
@@ -487,6 +524,19 @@ class FrontStoreStats(C.Structure):
     _fields_ = [("probes", C.c_uint64), ("collisions", C.c_uint64), ("cuts", C.c_uint64), ("asked", C.c_uint64), ("evaluations", C.c_uint64)]
 
 
+class FrontObservation(C.Structure):
+    """guber_front_observation_t"""
+    _fields_ = [("observed", C.c_uint64), ("skipped", C.c_uint64), ("dropped", C.c_uint64), ("generations", C.c_uint64), ("threshold", C.c_uint32),
+                ("n_slots", C.c_uint32), ("slot_w", C.c_void_p), ("slot_cap", C.c_uint32),
+                ("n", C.c_uint32), ("hash", C.c_void_p), ("count", C.c_void_p), ("cap", C.c_uint32)]
+
+
+class FrontRebalanceStats(C.Structure):
+    """guber_front_rebalance_stats_t"""
+    _fields_ = [("observed", C.c_uint64), ("dropped", C.c_uint64), ("moves_planned", C.c_uint32), ("buckets_moved", C.c_uint32),
+                ("cancelled", C.c_uint32), ("n_hot", C.c_uint32)]
+
+
 class Front:
     """guber_front_t (include/guber_gpu.h): generations of requests in ARRIVAL order, resident in HBM -> routed to the engines on the
     device (XXH64 + the placement's rule: WorkerPool.getWorker, workers.go:180-184) -> evaluated -> answered in ARRIVAL order
@@ -506,6 +556,9 @@ class Front:
         L.guber_front_probe_missing_dev.argtypes = [C.c_void_p, C.POINTER(GuberBatch), C.POINTER(FrontAsk)]
         L.guber_front_eval_store_dev.argtypes = [C.c_void_p, C.POINTER(GuberBatch), C.POINTER(GuberResult), C.POINTER(abi.GuberStoreEvents)]
         L.guber_front_store_stats.argtypes = [C.c_void_p, C.POINTER(FrontStoreStats)]
+        L.guber_front_observe.argtypes = [C.c_void_p, C.c_uint32]
+        L.guber_front_observation.argtypes = [C.c_void_p, C.POINTER(FrontObservation)]
+        L.guber_front_rebalance.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.POINTER(FrontRebalanceStats)]
         self.engines = list(engines)
         self.placement = placement
         hs = (C.c_void_p * len(self.engines))(*[e.h for e in self.engines])
@@ -554,6 +607,31 @@ class Front:
         st = FrontStoreStats()
         _check(lib().guber_front_store_stats(self.h, C.byref(st)))
         return {k: int(getattr(st, k)) for k, _ in FrontStoreStats._fields_}
+
+    def observe(self, every):
+        """guber_front_observe: every k-th generation the front routes is counted on the device (0: off)"""
+        _check(lib().guber_front_observe(self.h, every))
+
+    def observation(self):
+        """guber_front_observation: ends the window -> dict(observed, skipped, dropped, generations, threshold, slot_w uint32[n_slots],
+        candidates [(key hash, count)] of the keys at or above the threshold, in no particular order)"""
+        cap = 2048                                    # (FO_TOP_MAX: every key at the threshold has a place)
+        hh, cc = np.zeros(cap, np.uint64), np.zeros(cap, np.uint32)
+        ns = self.placement.n_slots() if self.placement is not None else 1
+        sw = np.zeros(ns, np.uint32)
+        o = FrontObservation(slot_w=sw.ctypes.data, slot_cap=ns, hash=hh.ctypes.data, count=cc.ctypes.data, cap=cap)
+        _check(lib().guber_front_observation(self.h, C.byref(o)))
+        assert o.n_slots == ns and o.n <= cap, (o.n_slots, ns, o.n)
+        cand = list(zip(hh[:o.n].tolist(), cc[:o.n].tolist()))
+        return dict(observed=int(o.observed), skipped=int(o.skipped), dropped=int(o.dropped), generations=int(o.generations), threshold=int(o.threshold),
+                    slot_w=sw, candidates=cand)
+
+    def rebalance(self, placement=None, heavy_fraction=0.125):
+        """guber_front_rebalance: one placement pass over the window -> dict of guber_front_rebalance_stats_t"""
+        placement = self.placement if placement is None else placement
+        st = FrontRebalanceStats()
+        _check(lib().guber_front_rebalance(self.h, placement.h if placement is not None else None, heavy_fraction, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in FrontRebalanceStats._fields_}
 
     def stream_handle(self):
         return lib().guber_front_stream(self.h)

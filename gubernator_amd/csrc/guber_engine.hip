@@ -211,13 +211,13 @@ struct guber_engine {
 
 enum { KT_FRONT = 0, KT_EVAL2, KT_RESOLVE, KT_HIST, KT_SCATTER0, KT_SCATTER, KT_HEADS, KT_EVAL, KT_FRONT_MULTI, KT_EVAL2_MULTI,
        KT_PART, KT_OWN, KT_EVAL3, KT_PART_MULTI, KT_OWN_MULTI, KT_EVAL3_MULTI, KT_EVALPART_MULTI, KT_FR_COUNT, KT_FR_SCAN, KT_FR_SCATTER, KT_FR_OUT,
-       KT_FR_ELECT, KT_FR_MISSING, KT_FR_ASK, KT_FR_OUT_STORE, KT_COUNT };   // (the front's kernels last: guber_profile_read's passes leave them out)
+       KT_FR_ELECT, KT_FR_MISSING, KT_FR_ASK, KT_FR_OUT_STORE, KT_FR_OBSERVE, KT_FR_OBSERVE_TOP, KT_COUNT };   // (the front's kernels last: guber_profile_read's passes leave them out)
 static_assert(KT_COUNT <= 32, "guber_engine::prof_* hold 32 kernels");
 static const char* const kKernelNames[KT_COUNT] = {"k_front", "k_eval2", "k_resolve", "k_hist", "k_scatter(first)",
                                                    "k_scatter", "k_heads", "k_eval", "k_front_multi", "k_eval2_multi",
                                                    "k_part", "k_own", "k_eval3", "k_part_multi", "k_own_multi", "k_eval3_multi", "k_evalpart_multi",
                                                    "k_fr_count", "k_fr_scan", "k_fr_scatter", "k_fr_out",
-                                                   "k_fr_elect", "k_fr_missing", "k_fr_ask", "k_fr_out_store"};
+                                                   "k_fr_elect", "k_fr_missing", "k_fr_ask", "k_fr_out_store", "k_fr_observe", "k_fr_observe_top"};
 
 static uint64_t take_stamps(guber_engine* e, uint64_t n) {
     const uint64_t b = e->seq_next;

@@ -21,6 +21,9 @@
 // of 40 000 +5 ... +10 %, of 57 000 -8 %.
 constexpr uint32_t FRONT_ONE_PAIR_MAX = 49152;
 struct guber_front {
+    // Lock order: fronts' mutexes first (a mesh takes its ranks' in rank order), then engines' in ADDRESS order (EngineLocks; guber_mesh_eval_small
+    // takes every front's and then every engine's that way).  guber_front_rebalance holds this mutex over its whole pass and takes engines only
+    // through EngineLocks and guber_move_items_by_hash, which takes its two in address order: it fits in.
     std::mutex mu;
     int device = 0;
     std::vector<guber_engine*> eng;
@@ -71,6 +74,18 @@ struct guber_front {
         uint32_t n = 0, cut_at = 0; const void *key_bytes = nullptr, *key_off = nullptr; int64_t now_ms = 0;
         uint64_t probes = 0, collisions = 0, cuts = 0, asked = 0, evals = 0;
     } st;
+    // The observation window (guber_front_observe / guber_front_observation / guber_front_rebalance; guber_kernels_front_observe.h), allocated
+    // by the first guber_front_observe(f, every > 0): the candidate table, the slots' words, the striped totals and the compaction's counter in
+    // ONE allocation (cleared by one memset at a window's end), and the pinned memory k_fr_observe_top reports into.
+    struct Observe {
+        uint32_t every = 0, since = 0, n_slots = 0, seq = 0; bool no_agg = false;
+        bool ahead_counted = false;                    // the generation routed ahead took its turn in "every k-th" when it was routed
+        bool skip_one = false;                         // ... and a pass dropped it: the call that routes it again does not count it again
+        DevBuf<uint8_t> mem; size_t mem_bytes = 0; FrObsCell* cell = nullptr; uint32_t* slot_w = nullptr; FrObsTot* tot = nullptr; uint32_t* n_top = nullptr;
+        CohBuf<uint8_t> host; CohBuf<FrontHost> word;
+        unsigned long long *h_hash = nullptr, *h_tot = nullptr; uint32_t *h_count = nullptr, *h_slot_w = nullptr;
+        uint64_t generations = 0;                      // the window's
+    } ob;
 };
 
 static size_t front_col(size_t bytes) { return (bytes + 63) & ~(size_t)63; }
@@ -127,6 +142,7 @@ extern "C" void guber_front_destroy(guber_front_t* f) {
         t.flags.release(); t.oflags.release(); t.after.release(); t.oafter.release(); t.ctl.release(); t.tabs.release();
         for (auto ev : t.ev) if (ev) (void)hipEventDestroy(ev);
     }
+    f->ob.mem.release(); f->ob.host.release(); f->ob.word.release();
     f->rt_table.release(); f->rt_exs.release(); f->rt_exh.release();
     if (f->rs2 && f->rs2 != f->rs) (void)hipStreamDestroy(f->rs2);
     if (f->os && f->os != f->rs) (void)hipStreamDestroy(f->os);
@@ -240,14 +256,17 @@ static int front_route_on(guber_front* f, hipStream_t st) {
 extern "C" int guber_front_set_rule(guber_front_t* f, const guber_route_rule_t* rule) {
     if (!f || !rule) return fail(GUBER_E_INVALID_ARG, "null argument");
     std::lock_guard<std::mutex> lk(f->mu);
+    if (f->ob.every && (uint64_t)rule->n_shards * rule->per != f->ob.n_slots) return fail(GUBER_E_INVALID_ARG, "guber_front: the rule's slots are counted by the observation window; guber_front_observe(f, 0) first");
     if (hipSetDevice(f->device) != hipSuccess) return fail(GUBER_E_HIP, "hipSetDevice");
     return front_set_rule(f, rule);
 }
 
-// k_fr_count, k_fr_scan and k_fr_scatter of generation g on its routing stream
-static int front_route(guber_front* f, guber_front::Slot& s, const FrontGen* fg, int64_t gen) {
+// k_fr_count, k_fr_scan and k_fr_scatter of generation g on its routing stream; observe: the generation counts for guber_front_observe's
+// "every k-th" (a store generation does not, nor does an empty one), and the k-th is counted behind its routing (k_fr_observe)
+static int front_route(guber_front* f, guber_front::Slot& s, const FrontGen* fg, int64_t gen, bool observe = true) {
     const guber_batch_t* b = &fg->b;
     hipStream_t rs = (gen & 1) ? f->rs2 : f->rs;
+    if (observe && f->ob.skip_one) { f->ob.skip_one = false; observe = false; }   // (routed ahead, counted then, dropped by a pass: see Observe)
     // the slot's previous generation has left it: its answers' way home read what this routing writes
     if (s.out_recorded) { HIPCHK(hipStreamWaitEvent(rs, s.ev_out, 0)); s.out_recorded = false; }
     s.gen = gen; s.n = b->n; s.dispatched = false;
@@ -278,6 +297,18 @@ static int front_route(guber_front* f, guber_front::Slot& s, const FrontGen* fg,
     e0->span_end();
     if (hipGetLastError() != hipSuccess) return fail(GUBER_E_HIP, "kernel launch");
     HIPCHK(hipEventRecord(s.ev_in, rs));
+    if (observe && f->ob.every && ++f->ob.since >= f->ob.every) {
+        // (behind the event: the generation's evaluation does not wait for it; the caller's arrays stay valid until guber_front_synchronize)
+        f->ob.since = 0; f->ob.generations++;
+        FrObs O{};
+        O.n = A.n; O.max_key = A.max_key; O.key_stride = A.key_stride; O.cmask = FO_CELLS - 1u; O.no_agg = f->ob.no_agg ? 1u : 0u;
+        O.key_bytes = A.key_bytes; O.key_off = A.key_off; O.key_len = A.key_len; O.behavior = A.behavior;
+        O.slot_w = f->ob.slot_w; O.cell = f->ob.cell; O.tot = f->ob.tot; O.R = A.R;
+        e0->span_begin(KT_FR_OBSERVE, b->n, rs);
+        hipLaunchKernelGGL(k_fr_observe, dim3(tiles), dim3(FR_TILE), 0, rs, O);
+        e0->span_end();
+        if (hipGetLastError() != hipSuccess) return fail(GUBER_E_HIP, "kernel launch");
+    }
     return 0;
 }
 
@@ -499,7 +530,7 @@ static int front_route_ahead(guber_front* f, const FrontGen* g) {
     if (f->pre_routed) return fail(GUBER_E_INVALID_ARG, "guber_front: a generation is routed ahead already");
     if (hipSetDevice(f->device) != hipSuccess) return fail(GUBER_E_HIP, "hipSetDevice");
     const int rc = front_route(f, f->slots[f->generations % f->depth], g, (int64_t)f->generations);
-    if (!rc) f->pre_routed = true;
+    if (!rc) { f->pre_routed = true; f->ob.ahead_counted = f->ob.every != 0 && g->b.n != 0; }
     return rc;
 }
 // have the shares' sizes of the generation routed ahead reached host memory?
@@ -586,7 +617,7 @@ static int front_probe_missing(guber_front* f, const FrontGen* g, guber_front_as
     guber_front::Slot& s = f->slots[f->generations % f->depth];
     guber_engine* e0 = f->eng[0];
     t.probed = false; f->pre_routed = false;
-    { const int rc = front_route(f, s, g, (int64_t)f->generations); if (rc) return rc; }
+    { const int rc = front_route(f, s, g, (int64_t)f->generations, false); if (rc) return rc; }
     t.probes++;
     t.n = n; t.cut_at = n; t.key_bytes = b.key_bytes; t.key_off = g->key_stride ? (const void*)g->key_len : (const void*)b.key_off; t.now_ms = b.now_ms;
     if (n == 0) { t.probed = true; f->pre_routed = true; return GUBER_OK; }
@@ -752,5 +783,159 @@ extern "C" int guber_front_stats(guber_front_t* f, guber_front_stats_t* out) {
     std::lock_guard<std::mutex> lk(f->mu);
     out->generations = f->generations; out->forced_flushes = f->forced_flushes; out->host_waits = f->host_waits;
     out->host_wait_us = (uint64_t)(f->host_wait_ms * 1e3);
+    return GUBER_OK;
+}
+
+// ---- online placement: the front observes its own traffic and runs placement passes (include/guber_gpu.h) ------------------------------
+// guber_front_observe turns the sampling on (front_route launches k_fr_observe behind every k-th generation's routing); a window ends in
+// guber_front_observation (tests, tools) or guber_front_rebalance, which drives the placement as GPUWorkerPool's passes do
+// (worker_pool.cpp: plan, migrate, cancel what could not be migrated, commit).
+static int front_observe_ensure(guber_front* f) {
+    auto& o = f->ob;
+    const uint32_t n_slots = f->rule.n_shards * f->rule.per;
+    if (o.mem.p && o.n_slots == n_slots) return 0;
+    for (hipStream_t st : {f->rs, f->rs2}) HIPCHK(hipStreamSynchronize(st));      // (a window counted under a rule of another size: nobody reads it any more)
+    auto carve = [&](uint8_t* base) {
+        ColCarver c{(uintptr_t)base};
+        o.cell = c.take<FrObsCell>(FO_CELLS); o.slot_w = c.take<uint32_t>(n_slots); o.tot = c.take<FrObsTot>(FO_STRIPES); o.n_top = c.take<uint32_t>(1);
+        return (size_t)(c.at - (uintptr_t)base);
+    };
+    auto carve_host = [&](uint8_t* base) {
+        ColCarver c{(uintptr_t)base};
+        o.h_hash = c.take<unsigned long long>(FO_TOP_MAX); o.h_tot = c.take<unsigned long long>(4); o.h_count = c.take<uint32_t>(FO_TOP_MAX); o.h_slot_w = c.take<uint32_t>(n_slots);
+        return (size_t)(c.at - (uintptr_t)base);
+    };
+    o.mem_bytes = carve(nullptr);
+    if (o.mem.ensure(o.mem_bytes) || o.host.ensure(carve_host(nullptr)) || o.word.ensure(1)) return GUBER_E_NOMEM;
+    carve(o.mem.p); carve_host(o.host.p);
+    memset((void*)o.word.p, 0, sizeof(FrontHost));
+    HIPCHK(hipMemsetAsync(o.mem.p, 0, o.mem_bytes, f->rs));
+    HIPCHK(hipStreamSynchronize(f->rs));
+    o.n_slots = n_slots; o.generations = 0; o.since = 0;
+    return 0;
+}
+extern "C" int guber_front_observe(guber_front_t* f, uint32_t every) {
+    if (!f) return fail(GUBER_E_INVALID_ARG, "null front");
+    std::lock_guard<std::mutex> lk(f->mu);
+    if (every == 0) { f->ob.every = 0; f->ob.since = 0; f->ob.skip_one = false; return GUBER_OK; }
+    if (f->eng.size() < 2 || !f->have_rule || f->rule.n_shards < 2) return fail(GUBER_E_INVALID_ARG, "guber_front_observe: a front of several engines with a placement's rule");
+    if (hipSetDevice(f->device) != hipSuccess) return fail(GUBER_E_HIP, "hipSetDevice");
+    const int rc = front_observe_ensure(f);
+    if (rc) return rc;
+    f->ob.no_agg = guber_lab_env("GUBER_FRONT_OBSERVE_NO_AGG") != nullptr;   // (the laboratory build's measure of the per-tile aggregation)
+    f->ob.every = every; f->ob.since = 0;
+    return GUBER_OK;
+}
+// (f->mu held, the device set, the window allocated) k_fr_observe_top behind everything the window's generations left on the routing
+// stream; on return its report is in f->ob's pinned memory, *n_top candidates of it, and the window's memory is being cleared on the stream
+static int front_observe_end(guber_front* f, uint32_t* n_top, uint32_t* threshold, uint64_t* generations) {
+    auto& o = f->ob;
+    hipStream_t rs = f->rs;
+    if (f->rs2 != rs) HIPCHK(hipStreamSynchronize(f->rs2));
+    // the bar needs the window's total: one small copy (the pass is synchronous anyway)
+    static_assert(sizeof(FrObsTot) == 32, "four words per stripe");
+    std::vector<FrObsTot> tot(FO_STRIPES);
+    HIPCHK(hipMemcpyAsync(tot.data(), o.tot, sizeof(FrObsTot) * FO_STRIPES, hipMemcpyDeviceToHost, rs));
+    HIPCHK(hipStreamSynchronize(rs));
+    uint64_t observed = 0;
+    for (auto& t : tot) observed += t.w[FO_OBSERVED];
+    // one eighth of the planner's default bar.  Fewer than 2 x engines x 64 keys can stand at or above it (FO_TOP_MAX's note): all are reported
+    static_assert(FO_TOP_MAX >= 2u * MULTI_MEM_MAX * 64u, "every key at the bar has a place in the report");
+    const uint64_t bar = std::max<uint64_t>(1, observed / ((uint64_t)f->eng.size() * 64u));
+    const uint32_t seq = ++o.seq ? o.seq : ++o.seq;
+    FrObsTop T{FO_CELLS, o.n_slots, (uint32_t)std::min<uint64_t>(bar, 0xffffffffu), seq, 0u, o.cell, o.slot_w, o.tot, o.n_top,
+               o.h_hash, o.h_count, o.h_slot_w, o.h_tot, &o.word.p->w[0]};
+    {
+        guber_engine* e0 = f->eng[0];
+        std::unique_lock<std::mutex> pl(e0->mu, std::defer_lock);
+        if (e0->profiling) pl.lock();
+        e0->span_begin(KT_FR_OBSERVE_TOP, FO_CELLS, rs);
+        hipLaunchKernelGGL(k_fr_observe_top, dim3(64), dim3(256), 0, rs, T);
+        e0->span_end();
+        T.phase = 1u;
+        e0->span_begin(KT_FR_OBSERVE_TOP, 0, rs);
+        hipLaunchKernelGGL(k_fr_observe_top, dim3(1), dim3(256), 0, rs, T);
+        e0->span_end();
+    }
+    if (hipGetLastError() != hipSuccess) return fail(GUBER_E_HIP, "kernel launch");
+    const int rc = route_wait_reported(o.word.p, 1, seq, f->device, rs, "guber_front: the observation window did not report");
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(o.mem.p, 0, o.mem_bytes, rs));             // the next window starts from zero
+    if (f->rs2 != rs) HIPCHK(hipStreamSynchronize(rs));              // (... also for an odd generation's k_fr_observe on a second routing stream)
+    *n_top = (uint32_t)o.word.p->w[0]; *threshold = T.threshold; *generations = o.generations;
+    o.generations = 0;
+    return 0;
+}
+extern "C" int guber_front_observation(guber_front_t* f, guber_front_observation_t* out) {
+    if (!f || !out) return fail(GUBER_E_INVALID_ARG, "null argument");
+    if ((out->slot_cap && !out->slot_w) || (out->cap && (!out->hash || !out->count))) return fail(GUBER_E_INVALID_ARG, "null observation arrays");
+    std::lock_guard<std::mutex> lk(f->mu);
+    auto& o = f->ob;
+    if (!o.mem.p) return fail(GUBER_E_INVALID_ARG, "guber_front_observation: guber_front_observe has never been turned on");
+    if (hipSetDevice(f->device) != hipSuccess) return fail(GUBER_E_HIP, "hipSetDevice");
+    uint32_t n_top = 0;
+    const int rc = front_observe_end(f, &n_top, &out->threshold, &out->generations);
+    if (rc) return rc;
+    out->observed = o.h_tot[0]; out->skipped = o.h_tot[1]; out->dropped = o.h_tot[2];
+    out->n_slots = o.n_slots; out->n = n_top;
+    if (out->slot_cap) memcpy(out->slot_w, o.h_slot_w, (size_t)std::min(out->slot_cap, o.n_slots) * 4);
+    if (out->cap) { memcpy(out->hash, o.h_hash, (size_t)std::min(out->cap, n_top) * 8); memcpy(out->count, o.h_count, (size_t)std::min(out->cap, n_top) * 4); }
+    return GUBER_OK;
+}
+extern "C" int guber_front_rebalance(guber_front_t* f, guber_placement_t* placement, double heavy_fraction, guber_front_rebalance_stats_t* out) {
+    if (out) *out = guber_front_rebalance_stats_t{};
+    if (!f || !placement || !out) return fail(GUBER_E_INVALID_ARG, "null argument");
+    uint32_t p_shards = 0, p_slots = 0, n_hot = 0;
+    if (guber_placement_info(placement, &p_shards, &p_slots, &n_hot)) return fail(GUBER_E_INVALID_ARG, "guber_front_rebalance: no placement");
+    std::lock_guard<std::mutex> lk(f->mu);
+    auto& o = f->ob;
+    if (f->eng.size() < 2 || !f->have_rule) return fail(GUBER_E_INVALID_ARG, "guber_front_rebalance: a front of several engines with a placement's rule");
+    if (p_shards != f->rule.n_shards || p_shards > f->eng.size() || p_slots != f->rule.n_shards * f->rule.per)
+        return fail(GUBER_E_INVALID_ARG, "guber_front_rebalance: not the placement the front's rule came from (shards, slots)");
+    if (!o.mem.p) return fail(GUBER_E_INVALID_ARG, "guber_front_rebalance: guber_front_observe has never been turned on");
+    if (hipSetDevice(f->device) != hipSuccess) return fail(GUBER_E_HIP, "hipSetDevice");
+    // a generation that was probed or routed ahead followed the rule that is about to change: whoever evaluates it routes it afresh
+    // (a probed one was never counted; one routed ahead while observation was on was: the call that routes it again must not count it twice)
+    if (f->pre_routed && !f->st.probed && o.ahead_counted) o.skip_one = true;
+    f->st.probed = false; f->pre_routed = false; o.ahead_counted = false;
+    {
+        // every generation in flight, on every slot: what another call holds back for these tables goes first, then the streams run dry
+        const int ne = (int)f->eng.size();
+        EngineLocks locks(ne, [&](int i) { return f->eng[i]; });
+        locks.launch_held_by_others();
+        for (auto st : f->streams) HIPCHK(hipStreamSynchronize(st));
+        for (hipStream_t st : {f->rs, f->rs2, f->os}) HIPCHK(hipStreamSynchronize(st));
+    }
+    uint32_t n_top = 0, threshold = 0; uint64_t generations = 0;
+    int rc = front_observe_end(f, &n_top, &threshold, &generations);
+    if (rc) return rc;
+    out->observed = o.h_tot[0]; out->dropped = o.h_tot[2];
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the candidates' hashes as the placement takes them");
+    if (guber_placement_observe_aggregate(placement, o.h_slot_w, o.n_slots, (const uint64_t*)o.h_hash, o.h_count, n_top))
+        return fail(GUBER_E_INVALID_ARG, "guber_front_rebalance: the placement did not take the window");
+    guber_placement_move_t moves[64];
+    uint32_t nm = 0;
+    rc = guber_placement_plan(placement, heavy_fraction, moves, 64, &nm);
+    if (rc) return fail(rc, "guber_front_rebalance: guber_placement_plan");
+    nm = std::min(nm, 64u);
+    out->moves_planned = nm;
+    for (uint32_t q = 0; q < nm; ++q) {
+        // (guber_move_items_by_hash takes its two engines in address order: the order next to the front's mutex)
+        uint32_t moved = 0;
+        int mrc = GUBER_E_INVALID_ARG;
+        if (moves[q].from < f->eng.size() && moves[q].to < f->eng.size())
+            mrc = guber_move_items_by_hash(f->eng[moves[q].from], f->eng[moves[q].to], &moves[q].key_hash, 1, &moved);
+        if (mrc) { (void)guber_placement_cancel(placement, moves[q].key_hash); out->cancelled++; }   // (what was not taken is back in its table)
+        else out->buckets_moved++;
+    }
+    rc = guber_placement_commit(placement);
+    guber_route_rule_t rule;
+    if (!rc) rc = guber_placement_export(placement, &rule);
+    if (rc) return fail(rc, "guber_front_rebalance: commit / export");
+    rule.global_engine = f->rule.global_engine;
+    rc = front_set_rule(f, &rule);
+    if (rc) return rc;
+    (void)guber_placement_info(placement, nullptr, nullptr, &n_hot);
+    out->n_hot = n_hot;
     return GUBER_OK;
 }

@@ -28,6 +28,17 @@ struct RouteArgs {
     uint32_t* counts; unsigned int* done;                                            // host: the shares' sizes, then the flag (= seq)
     RouteRule R;
 };
+// the placement slot of a hash (guber_placement_impl.h slot_of): route_engine's index into the slot table, and what the front's observation
+// counts per slot (k_fr_observe, guber_kernels_front_observe.h) — one text for both
+__device__ __forceinline__ uint32_t route_slot(const RouteRule& R, const unsigned long long h) {
+    const unsigned long long h63 = h >> 1;
+    unsigned long long w = __umul64hi(h63, R.inv_step);
+    if ((w + 1) * R.step <= h63) ++w;
+    if (w >= R.n_shards) w = R.n_shards - 1;
+    unsigned long long sub = __umul64hi(h63 - w * R.step, R.inv_sub);
+    if (sub >= R.per) sub = R.per - 1;
+    return (uint32_t)(w * R.per + sub);
+}
 __device__ __forceinline__ uint32_t route_engine(const RouteRule& R, const unsigned long long h) {
     if (R.ex_n) {
         for (uint32_t i = (uint32_t)((h * 0x9E3779B97F4A7C15ull) >> 56) & (R.ex_cells - 1);; i = (i + 1) & (R.ex_cells - 1)) {
@@ -36,13 +47,7 @@ __device__ __forceinline__ uint32_t route_engine(const RouteRule& R, const unsig
             if (x == 0ull) break;
         }
     }
-    const unsigned long long h63 = h >> 1;
-    unsigned long long w = __umul64hi(h63, R.inv_step);
-    if ((w + 1) * R.step <= h63) ++w;
-    if (w >= R.n_shards) w = R.n_shards - 1;
-    unsigned long long sub = __umul64hi(h63 - w * R.step, R.inv_sub);
-    if (sub >= R.per) sub = R.per - 1;
-    return R.table[(uint32_t)(w * R.per + sub)];
+    return R.table[route_slot(R, h)];
 }
 // the columns the routing reads, brought to HBM first as full coalesced lines (XXH64 straight out of host memory would be a few small
 // dependent PCIe reads per request: measured 4x the whole batch's time); the keys stay there for guber_stage_submit_routed

@@ -59,10 +59,9 @@ extern "C" uint32_t guber_placement_shard(const guber_placement_t* p, uint64_t k
 }
 extern "C" uint32_t guber_placement_version(const guber_placement_t* p) { return p ? p->version.load(std::memory_order_acquire) : 0; }
 
-extern "C" void guber_placement_observe(guber_placement_t* p, uint64_t h, uint32_t weight) {
-    if (!p || weight == 0) return;
-    p->slot_w[p->slot_of(h)].fetch_add(weight, std::memory_order_relaxed);   // (the total is the sum of these: no shared hot word)
-    for (uint32_t row = 0; row < kSketchRows; ++row) {       // Misra-Gries, one counter per cell: the cell's majority key survives
+// the sketch's part of guber_placement_observe: Misra-Gries, one counter per cell — the cell's majority key survives
+static void sketch_add(guber_placement* p, uint64_t h, uint32_t weight) {
+    for (uint32_t row = 0; row < kSketchRows; ++row) {
         Cell& c = p->sketch[((size_t)row << kSketchBits) + sketch_cell(h, row)];
         const uint64_t cur = c.h.load(std::memory_order_relaxed);
         const uint32_t cnt = c.c.load(std::memory_order_relaxed);
@@ -70,6 +69,22 @@ extern "C" void guber_placement_observe(guber_placement_t* p, uint64_t h, uint32
         else if (cnt <= weight) { c.h.store(h, std::memory_order_relaxed); c.c.store(weight - cnt, std::memory_order_relaxed); }
         else c.c.store(cnt - weight, std::memory_order_relaxed);
     }
+}
+extern "C" void guber_placement_observe(guber_placement_t* p, uint64_t h, uint32_t weight) {
+    if (!p || weight == 0) return;
+    p->slot_w[p->slot_of(h)].fetch_add(weight, std::memory_order_relaxed);   // (the total is the sum of these: no shared hot word)
+    sketch_add(p, h, weight);
+}
+
+// Traffic that was reduced elsewhere (a front's observation window, guber_front_rebalance): the requests per slot as counted there — the
+// candidates' requests are among them — and the keys that may be heavy with their counts, which go into the sketch alone.
+extern "C" int guber_placement_observe_aggregate(guber_placement_t* p, const uint32_t* slot_w, uint32_t n_slots, const uint64_t* hashes,
+                                                 const uint32_t* counts, uint32_t n) {
+    if (!p || (n_slots && !slot_w) || (n && (!hashes || !counts))) return GUBER_E_INVALID_ARG;
+    if (n_slots != p->n_slots) return GUBER_E_INVALID_ARG;
+    for (uint32_t s = 0; s < n_slots; ++s) if (slot_w[s]) p->slot_w[s].fetch_add(slot_w[s], std::memory_order_relaxed);
+    for (uint32_t k = 0; k < n; ++k) if (counts[k] && hashes[k]) sketch_add(p, hashes[k], counts[k]);
+    return GUBER_OK;
 }
 
 extern "C" int guber_placement_route_keys(const guber_placement_t* p, const uint8_t* key_bytes, const uint32_t* key_off, uint32_t n,

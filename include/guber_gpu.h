@@ -688,6 +688,56 @@ int guber_placement_export(const guber_placement_t* p, struct guber_route_rule* 
  * lost.  (A key longer than the staging row — min(max_key_bytes of the two) + 16 bytes, rounded up to a multiple of 8 — is not taken out in
  * the first place: it stays in `from` and is not reported.)  Moved buckets count against `to`'s cache_size like added items: its next call evicts. */
 int guber_move_items_by_hash(guber_engine_t* from, guber_engine_t* to, const uint64_t* key_hashes, uint32_t n, uint32_t* moved);
+/* Traffic that was counted elsewhere (a front's observation window, below): slot_w[n_slots] = requests per slot, the candidates' requests
+ * among them, added as given; hashes / counts [n] = keys that may be heavy, fed to the heavy-hitter sketch with their counts as weights
+ * (not to the slots again).  GUBER_E_INVALID_ARG when n_slots is not the placement's. */
+int guber_placement_observe_aggregate(guber_placement_t* p, const uint32_t* slot_w, uint32_t n_slots, const uint64_t* hashes,
+                                      const uint32_t* counts, uint32_t n);
+
+/* ---- online placement for a front (guber_front_t above): getWorker's choice (workers.go:180-184) refitted to the traffic the front itself
+ *      routes.  Opt-in: a front that never enables observation launches exactly what it launched before.
+ *        guber_front_observe(f, every)   every = 0 (the state a front is created in): off.  every = k: every k-th generation the front routes
+ *                                        is also counted on the device (k_fr_observe on the routing stream): requests per placement slot and
+ *                                        per hot-key candidate, over a window that lasts until one of the two calls below ends it.  Requests
+ *                                        whose engine does not depend on the hash are left out and counted as skipped: Behavior_GLOBAL ones
+ *                                        when the rule names a global_engine, empty keys, keys above the engines' max_key_bytes.  NOT
+ *                                        observed: store generations (guber_front_probe_missing_dev) and the one-launch path of a mesh
+ *                                        (guber_mesh_eval_small); an EMPTY generation is neither counted nor takes a turn in "every k-th".
+ *                                        A generation that was routed ahead and that a pass dropped is counted once, when it was routed
+ *                                        first.  GUBER_E_INVALID_ARG on a front of one engine or without a rule; while
+ *                                        observation is on, guber_front_set_rule refuses a rule with another number of slots.
+ *        guber_front_observation         synchronous, for tests and tools: ends the window and returns it; feeds no placement.  slot_w
+ *                                        (optional, slot_cap entries) takes the slots' counts, hash / count (optional, cap entries) the keys
+ *                                        with at least `threshold` = max(1, observed / (engines x 64)) requests, in no particular order;
+ *                                        n_slots and n say how many there are.  Fewer than 2 x engines x 64 keys can stand at the
+ *                                        threshold (it is rounded down), at most 2 047 on sixteen engines: every one of them is reported.
+ *        guber_front_rebalance           one placement pass, under the front's lock: waits for every generation in flight (a probed or
+ *                                        routed-ahead generation is dropped and routed afresh by the call that evaluates it), ends the
+ *                                        window, feeds it to `placement` (guber_placement_observe_aggregate), plans at most 64 moves
+ *                                        (guber_placement_plan: the slot table stays), migrates each moving key's bucket
+ *                                        (guber_move_items_by_hash; a move the destination refuses is cancelled: guber_placement_cancel),
+ *                                        commits, and gives the front the new rule (its global_engine is kept).  `placement` is the one the
+ *                                        front's rule came from: as many shards as the rule, as many slots.  The caller keeps other users of
+ *                                        the front's ENGINES away for the call, as for guber_move_items_by_hash.  Fronts under a mesh may be
+ *                                        rebalanced between the mesh's calls. */
+typedef struct guber_front_observation {
+    uint64_t observed, skipped, dropped;   /* requests counted; left out (see above); counted in their slot but in no candidate cell */
+    uint64_t generations;                  /* generations the window saw */
+    uint32_t threshold;
+    uint32_t n_slots; uint32_t* slot_w; uint32_t slot_cap;
+    uint32_t n; uint64_t* hash; uint32_t* count; uint32_t cap;
+} guber_front_observation_t;
+typedef struct guber_front_rebalance_stats {
+    uint64_t observed;         /* requests the window counted */
+    uint64_t dropped;          /* ... of which in no candidate cell (the candidate table was crowded around them) */
+    uint32_t moves_planned;    /* keys whose engine was to change */
+    uint32_t buckets_moved;    /* moves carried out (a key that was not resident had nothing to move and counts) */
+    uint32_t cancelled;        /* moves the destination refused: the key stays where it was */
+    uint32_t n_hot;            /* keys placed individually after the pass */
+} guber_front_rebalance_stats_t;
+int guber_front_observe(guber_front_t* f, uint32_t every);
+int guber_front_observation(guber_front_t* f, guber_front_observation_t* out);
+int guber_front_rebalance(guber_front_t* f, guber_placement_t* placement, double heavy_fraction /* <= 0: 0.125 */, guber_front_rebalance_stats_t* out);
 /* The HIP stream the engine enqueues on (hipStream_t), to be handed to guber_config_t.stream of further engines: engines that
  * share device and stream can share launches (guber_stages_submit, guber_eval_batches_routed_dev).  The engine that owns the
  * stream must be destroyed last. */
